@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — device-resident ncclAllReduce bus bandwidth of the MI355X engine (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the last step's output (--dump-outputs) and prints the
+result line: `value`, `ms_per_step` and the roofline figures that follow from the timed loop alone. --full adds
+everything that takes runs of its own: the exactness check (`check`), the CPU baseline, the N = 1 extras (64 MiB,
+hipMemcpy D2D, cold buffers), the link probe and the suite (N > 1) and the host-staged bucket.
 
 One "step" = one ncclAllReduce(sum, fp32) of the per-rank buffer, inputs already resident in HBM.
 Workload (BASELINE.json metric: 256 MiB fp32 at 1/2/4/8 GPUs):
@@ -96,12 +101,43 @@ def parse(argv=None):
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=10)
     p.add_argument("--size-mib", type=int, default=0, help="override per-rank buffer size")
-    p.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample budget")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extra", action="store_true", help="skip the secondary 256 MiB n=1 measurement")
-    p.add_argument("--no-suite", action="store_true", help="N>1: skip BASELINE configs 3-5 + link probes")
-    p.add_argument("--quick-suite", action="store_true", help="N>1: smaller suite (rehearsal on one GPU)")
-    return p.parse_args(argv)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline: the exactness check, the CPU baseline, the N=1 "
+                        "extras, the link probe and suite (N>1) and the host-staged bucket; the options below "
+                        "trim that run")
+    p.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU baseline sample budget")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    p.add_argument("--no-extra", action="store_true", help="--full: skip the secondary 256 MiB n=1 measurement")
+    p.add_argument("--no-suite", action="store_true", help="--full, N>1: skip BASELINE configs 3-5 + link probes")
+    p.add_argument("--quick-suite", action="store_true", help="--full, N>1: smaller suite (rehearsal on one GPU)")
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_SEED = 0xD0F5                 # --dump-outputs: which elements of a large output are sampled
+DUMP_WHOLE_BYTES = 32 * MIB        # outputs up to this size are written whole ...
+DUMP_SAMPLE_ELEMS = 4 << 20        # ... larger ones as this many elements (16 MiB of fp32), far below 64 MB in all
+
+
+def dump_outputs(path: str, recv) -> None:
+    """--dump-outputs: the receive buffer of the last timed step (what the caller of ncclAllReduce gets back) as
+    DIR/allreduce_recv.npy, float32. A buffer above DUMP_WHOLE_BYTES is written as a fixed sample: the elements at
+    DUMP_SAMPLE_ELEMS indices drawn once from numpy's PCG64 seeded with DUMP_SEED (sorted; the same indices in every
+    run of the same size), so two builds are compared element for element on the same positions."""
+    import numpy as np
+    import torch
+    count = recv.numel()
+    if count * recv.element_size() <= DUMP_WHOLE_BYTES:
+        out = recv.detach().cpu().numpy()
+    else:
+        idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).integers(0, count, DUMP_SAMPLE_ELEMS))
+        out = recv[torch.from_numpy(idx).to(recv.device)].cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "allreduce_recv.npy"), np.ascontiguousarray(out, dtype=np.float32))
 
 
 def _time_ms(fn, stream, iters: int, warmup: int = 3, align=None) -> float:
@@ -808,6 +844,8 @@ def main(argv=None):
     workload = (f"ncclAllReduce sum fp32, {size_mib} MiB, world_size=1 (the metric's size at N=1)" if n == 1 else
                 f"ncclAllReduce sum fp32, {size_mib} MiB per rank, {n}xMI355X direct scatter-reduce-gather")
     stream = torch.cuda.current_stream()
+    # the same inputs in every run with the same arguments (--dump-outputs compares two builds output for output)
+    torch.manual_seed(0x5EED0000 + rank)
     send = torch.empty(count, dtype=torch.float32, device="cuda").uniform_(-1, 1)
     recv = torch.empty_like(send)
 
@@ -836,22 +874,30 @@ def main(argv=None):
     gpu_ms = e0.elapsed_time(e1) / args.steps
     wall, gpu_ms = max_over_ranks(dist, [wall, gpu_ms])
     err = comm.async_error()
+    if args.dump_outputs and rank == 0:  # every rank of an AllReduce receives the same array
+        dump_outputs(args.dump_outputs, recv)
 
-    # size-independent correctness property at full size: dyadic inputs => exact sums
-    g = torch.Generator(device="cuda")
-    g.manual_seed(1234)
-    base = torch.randint(-1024, 1025, (count,), device="cuda", generator=g, dtype=torch.int32).float() / 256
-    send.copy_(base * (rank + 1))
-    step()
-    torch.cuda.synchronize()
-    want = base * (n * (n + 1) / 2)
-    err2 = comm.async_error()
-    ok = bool(torch.equal(recv, want)) and err == 0 and err2 == 0
+    # a plain run ends here with the result line; everything below this flag is the --full run's
+    full = args.full
+    ok = err == 0
     if not ok:
-        bad = (recv != want).nonzero().flatten()
-        print(f"[rank {rank}] CHECK FAILED: async errors {err}/{err2}, {bad.numel()} mismatches of {count}; "
-              f"first idx {bad[:8].tolist()} got {recv[bad[:4]].tolist()} want {want[bad[:4]].tolist()}; "
-              f"block size {count // n}", file=sys.stderr, flush=True)
+        print(f"[rank {rank}] async error {err} after the timed steps", file=sys.stderr, flush=True)
+    if full:
+        # size-independent correctness property at full size: dyadic inputs => exact sums
+        g = torch.Generator(device="cuda")
+        g.manual_seed(1234)
+        base = torch.randint(-1024, 1025, (count,), device="cuda", generator=g, dtype=torch.int32).float() / 256
+        send.copy_(base * (rank + 1))
+        step()
+        torch.cuda.synchronize()
+        want = base * (n * (n + 1) / 2)
+        err2 = comm.async_error()
+        ok = bool(torch.equal(recv, want)) and err == 0 and err2 == 0
+        if not ok:
+            bad = (recv != want).nonzero().flatten()
+            print(f"[rank {rank}] CHECK FAILED: async errors {err}/{err2}, {bad.numel()} mismatches of {count}; "
+                  f"first idx {bad[:8].tolist()} got {recv[bad[:4]].tolist()} want {want[bad[:4]].tolist()}; "
+                  f"block size {count // n}", file=sys.stderr, flush=True)
     if dist is not None:
         t = torch.tensor([0 if ok else 1], dtype=torch.int32)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -888,7 +934,7 @@ def main(argv=None):
         meas = None
         # ranks on separate GPUs: a real xGMI measurement, taken while every rank waits at a host barrier
         # (no peer kernel spinning on its GPU or moving bytes over the links during the probe)
-        probe = probe_links
+        probe = probe_links and full  # (the probe is a run of its own: --full)
         if probe:
             barrier()
         if rank == 0 and probe:
@@ -899,7 +945,7 @@ def main(argv=None):
             peak, basis, pr = meas["peak"], meas["peak_basis"], meas["probe"]
         else:
             peak, pr = round(spec_peak, 1), None
-            basis = ("spec/2: " + (f"{n - 1} links x {XGMI_LINK_GBPS_DIR} GB/s per direction" if probe else
+            basis = ("spec/2: " + (f"{n - 1} links x {XGMI_LINK_GBPS_DIR} GB/s per direction" if probe_links else
                                    "the ranks share one GPU here, no link exists to measure") +
                      (f" ({meas['error']})" if meas and "error" in meas else ""))
         roof = {"bound": "xgmi", "achieved": round(bus_rate, 1), "peak": peak, "unit": "GB/s",
@@ -913,7 +959,7 @@ def main(argv=None):
             roof["probe"] = pr
 
     extra = {}
-    if n == 1 and not args.no_extra and rank == 0:
+    if full and n == 1 and not args.no_extra and rank == 0:
         # configs[0] (64 MiB loopback, fits the 256 MiB Infinity Cache) and hipMemcpyAsync D2D of the
         # headline size (the reference's own nranks==1 implementation, onerank.cu:52-56) side by side
         small = 64 * MIB // 4
@@ -957,13 +1003,13 @@ def main(argv=None):
     # would change. Measured on the one-GPU rehearsal: once a rank process holds three or more hardware queues, every
     # later small collective takes ~27.6 us instead of ~4 us (profiles/r04_queue_order_n2_onegpu.txt).
     # BENCH_HOST_STAGED=first (diagnostics) runs it before the suite instead.
-    if not args.no_extra and n > 1 and os.environ.get("BENCH_HOST_STAGED") == "first":
+    if full and not args.no_extra and n > 1 and os.environ.get("BENCH_HOST_STAGED") == "first":
         run_host_staged()
 
     # the host-core baseline on rank 0 at every N (north_star: "in the same run"), while the other ranks wait at the
     # barrier below — it never overlaps a timed part of any rank
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if full and rank == 0 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(count, args.cpu_seconds)
         except Exception as e:  # the baseline is reported, never required
@@ -1002,7 +1048,7 @@ def main(argv=None):
             "metric": METRIC, "value": round(value, 2), "unit": "GB/s", "n_gpus": n, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 5), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic: uniform[-1,1) fp32 per rank generated on device (torch RNG)",
+            "data": "synthetic: uniform[-1,1) fp32 per rank generated on device (torch RNG, seeded per rank)",
             "config": {"workload": workload, "collective": "ncclAllReduce", "op": "sum", "bytes_per_rank": S,
                        "count": count, "n_ranks": n, "out_of_place": True,
                        "value_definition": ("HBM GB/s = 2S/t (n=1: busBW = algBW x 2(n-1)/n is 0 by definition)"
@@ -1010,10 +1056,12 @@ def main(argv=None):
                                             "1450-1492, the nccl-tests figure); busbw_sum_GBps = N x busBW")},
             "algbw_GBps": round(algbw, 2), "busbw_GBps": round(busbw, 2),
             **({"busbw_sum_GBps": round(n * busbw, 2)} if n > 1 else {}),
-            "roofline": roof, "cpu_baseline": cpu, "check": "pass" if ok else "FAIL", **link_summary(), **extra,
+            "roofline": roof, "cpu_baseline": cpu,
+            "check": "FAIL" if not ok else "pass" if full else "not run (--full runs the exactness check)",
+            **(link_summary() if full else {}), **extra,
         }
 
-    if n > 1 and not args.no_suite:
+    if full and n > 1 and not args.no_suite:
         # The suite (secondary measurements) runs under a watchdog: if any part of it stalls, every rank
         # still ends and rank 0 still prints the headline line, with the parts that finished.
         import threading
@@ -1052,7 +1100,7 @@ def main(argv=None):
         barrier()
         done.set()
         suite["seconds"] = round(time.perf_counter() - t_suite, 1)
-    if not args.no_extra and (n == 1 or os.environ.get("BENCH_HOST_STAGED") != "first"):
+    if full and not args.no_extra and (n == 1 or os.environ.get("BENCH_HOST_STAGED") != "first"):
         run_host_staged()
 
     if rank == 0:

@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 for rep in $(seq ${REPS:-3}); do
   for vs in ${VARIANTS:-10 0}; do
     v=${vs%%:*}; sh=12; [[ $vs == *:* ]] && sh=${vs##*:}
-    NCCL_AMD_COPY_VARIANT=$v NCCL_AMD_COPY_XCD_SHIFT=$sh timeout -k 10 240 python3 bench.py --steps 50 --warmup 10 --no-cpu-baseline \
+    NCCL_AMD_COPY_VARIANT=$v NCCL_AMD_COPY_XCD_SHIFT=$sh timeout -k 10 240 python3 bench.py --steps 50 --warmup 10 --full --no-cpu-baseline \
       > gpurun_out/copy_ab_${v}_${sh}_${rep}.log 2>&1 || { echo "variant $vs rep $rep FAILED"; exit 1; }
     python3 - "$vs" gpurun_out/copy_ab_${v}_${sh}_${rep}.log <<'PY'
 import json, sys

@@ -9,7 +9,7 @@ export NCCL_AMD_SPIN_TIMEOUT_MS=20000 BENCH_SWEEP_COLS=ll,default
 run() {  # name, then env assignments
   local name=$1; shift
   env "$@" timeout -k 10 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port $((29500 + RANDOM % 1000)) bench.py --gpus 2 --steps 3 --warmup 1 --quick-suite --no-cpu-baseline \
+    --master-port $((29500 + RANDOM % 1000)) bench.py --gpus 2 --steps 3 --warmup 1 --full --quick-suite --no-cpu-baseline \
     > $O/$name.log 2>&1 || { echo "$name FAILED"; tail -5 $O/$name.log; return 1; }
   python3 - "$name" "$O/$name.log" <<'PY'
 import json, sys

@@ -102,6 +102,26 @@ def test_size_table_row_from_sweep():
     assert bench.size_table_row(2, sweep)["file_line"] == "2 - - 32K"
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: a small output is written whole; a larger one as the same seeded, sorted sample of its
+    elements in every call (so two builds compare the same positions), float32, well under 64 MB."""
+    import numpy as np
+    import torch
+    import bench
+    small = torch.arange(1000, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    assert np.array_equal(np.load(tmp_path / "a" / "allreduce_recv.npy"), small.numpy())
+    count = bench.DUMP_WHOLE_BYTES // 4 + 7            # the first size that is sampled
+    big = torch.arange(count, dtype=torch.float32)      # element i holds i (exact in fp32 below 2^24)
+    bench.dump_outputs(str(tmp_path / "b"), big)
+    bench.dump_outputs(str(tmp_path / "c"), big)
+    b, c = np.load(tmp_path / "b" / "allreduce_recv.npy"), np.load(tmp_path / "c" / "allreduce_recv.npy")
+    assert b.dtype == np.float32 and b.shape == (bench.DUMP_SAMPLE_ELEMS,) and b.nbytes <= 64e6
+    assert np.array_equal(b, c) and np.all(np.diff(b) >= 0) and b[0] >= 0 and b[-1] < count
+    assert len(np.unique(b)) > 0.7 * b.size             # spread over the array, not one corner
+    assert b[-1] - b[0] > 0.99 * count
+
+
 def test_scale_decisions_tool_reads_bench_lines():
     """scripts/scale_decisions.py (the round-6 reading of the first 8-GPU SCALE record) finds bench lines wherever
     they sit in a record and calls a difference only outside both columns' spreads."""

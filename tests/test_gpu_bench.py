@@ -27,7 +27,7 @@ def test_bench_two_ranks_quick(built):
     env.pop("NCCL_AMD_EAGER_REGISTER", None)  # the library's defaults, as the driver runs it
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--quick-suite", "--cpu-seconds", "1"]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--quick-suite", "--cpu-seconds", "1"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -75,7 +75,8 @@ def test_bench_one_gpu_line(built):
     """The N=1 line (a short run): HBM roofline of the one-rank copy kernel, named from the run, with the
     cold-buffer fraction beside the headline one."""
     env = dict(os.environ, NCCL_AMD_SPIN_TIMEOUT_MS="20000")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--cpu-seconds", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--full",
+           "--cpu-seconds", "1"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -90,6 +91,37 @@ def test_bench_one_gpu_line(built):
     hs = d["host_staged"]
     assert hs["pipelined"]["check"] == "pass" and hs["direct"]["check"] == "pass", hs
     assert hs["direct"]["ms_per_step"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_output(built, tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline fields, runs none of the secondary
+    parts, and --dump-outputs writes the last timed step's receive buffer as float32. At world size 1 the AllReduce
+    is a copy, so the dump must equal the seeded input bit for bit — which also pins the inputs from run to run.
+    8 MiB: written whole (the seeded sample of larger outputs is a host-side index draw, checked on the CPU)."""
+    import numpy as np
+    import torch
+    env = dict(os.environ, NCCL_AMD_SPIN_TIMEOUT_MS="20000")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+           "--size-mib", "8", "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 1 and d["dtype"] == "f32"
+    assert d["unit"] == "GB/s" and d["higher_is_better"] is True and d["ms_per_step"] > 0
+    # value = the HBM rate 2S/t of the timed steps (n = 1); both figures are rounded in the line
+    assert abs(d["value"] / (2 * 8 * 2**20 / (d["ms_per_step"] * 1e-3) / 1e9) - 1) < 0.01
+    assert "copyKernel" in d["roofline"]["kernel"] and d["roofline"]["bound"] == "hbm"
+    # nothing beside the headline ran
+    assert d["cpu_baseline"] is None and "host_staged" not in d and "frac_cold" not in d["roofline"], d
+    assert d["check"].startswith("not run"), d["check"]
+    assert sorted(os.listdir(tmp_path)) == ["allreduce_recv.npy"]
+    got = np.load(tmp_path / "allreduce_recv.npy")
+    assert got.dtype == np.float32 and got.shape == (8 * 2**20 // 4,)
+    torch.manual_seed(0x5EED0000)  # bench.py's input of rank 0
+    want = torch.empty(got.size, dtype=torch.float32, device="cuda").uniform_(-1, 1).cpu().numpy()
+    assert np.array_equal(got, want)
 
 
 def test_bench_reports_a_failed_init(built):
