@@ -23,7 +23,7 @@ DEVOBJ   := $(DEVSRC:%.hip=$(BUILD)/%.o)
 HDRS     := $(wildcard $(SRCDIR)/*.h) include/nccl.h
 
 all: lib oracle numerics-host bootstrap-test tuner-test nccl-perf comm-examples plan-test mapcheck-test xgmi-probe atomicity-probe \
-     fp8-probe release-probe reuse-probe export-check-test barrier-probe
+     fp8-probe release-probe reuse-probe export-check-test barrier-probe bcast-plan-test bcast-example
 
 .PHONY: export-check-test
 export-check-test: tests/native/export_check_test
@@ -119,6 +119,24 @@ tests/native/plan_test: tests/native/plan_test.cc $(SRCDIR)/enqueue.cc $(SRCDIR)
 
 .PHONY: plan-test
 
+# CPU test driver of the Broadcast plan and of the partition its kernels walk (device_abi.h blockLenOf / sliceBounds /
+# llPartBounds, called from both sides); stubs like plan_test's
+bcast-plan-test: tests/native/bcast_plan_test
+
+tests/native/bcast_plan_test: tests/native/bcast_plan_test.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
+	$(CXX) -O1 -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -o $@ tests/native/bcast_plan_test.cc \
+	  $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
+
+.PHONY: bcast-plan-test
+
+# a C-ABI caller of ncclBroadcast / ncclBcast written against include/nccl.h only (links with -lnccl alone)
+bcast-example: tests/native/bcast_example
+
+tests/native/bcast_example: tests/native/bcast_example.cc include/nccl.h $(LIBDIR)/libnccl.so
+	$(HIPCC) -O2 --offload-arch=$(ARCH) -Iinclude -o $@ $< -L$(LIBDIR) -lnccl -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
+
+.PHONY: bcast-example
+
 # Host sanitizer builds (SURVEY §5 race detection; tests/test_sanitizers.py): the bootstrap, the IPC fd server
 # and the planning code under ASan+UBSan and, separately, TSan. Host code only — no GPU code is instrumented.
 SANCXX   := $(CXX) -g -O1 -fno-omit-frame-pointer -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude
@@ -126,7 +144,7 @@ ASAN     := -fsanitize=address,undefined -fno-sanitize-recover=undefined
 TSAN     := -fsanitize=thread
 HIPRT    := -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib
 SANBIN   := build/asan/bootstrap_test build/asan/plan_test build/asan/ipc_server_test \
-            build/tsan/bootstrap_test build/tsan/ipc_server_test
+            build/tsan/bootstrap_test build/tsan/ipc_server_test build/asan/bcast_plan_test
 sanitize: $(SANBIN)
 
 build/asan/bootstrap_test build/tsan/bootstrap_test: tests/native/bootstrap_test.cc $(SRCDIR)/bootstrap.cc $(SRCDIR)/debug.cc $(HDRS)
@@ -143,6 +161,10 @@ build/asan/ipc_server_test build/tsan/ipc_server_test: tests/native/ipc_server_t
 tests/native/export_check_test: tests/native/export_check_test.cc $(SRCDIR)/ipc.cc $(SRCDIR)/debug.cc $(HDRS)
 	$(CXX) -O1 -g -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -o $@ tests/native/export_check_test.cc \
 	  $(SRCDIR)/ipc.cc $(SRCDIR)/debug.cc -lpthread $(HIPRT)
+
+build/asan/bcast_plan_test: tests/native/bcast_plan_test.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SANCXX) $(ASAN) -o $@ tests/native/bcast_plan_test.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
 
 build/asan/plan_test: tests/native/plan_test.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
 	@mkdir -p $(dir $@)

@@ -254,6 +254,18 @@ ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t count, nccl
 ncclResult_t pncclReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
                          ncclRedOp_t op, int root, ncclComm_t comm, hipStream_t stream);
 
+/* nccl.h.in:469-483 — copies count elements from `root`'s sendbuff to every rank's recvbuff. sendbuff is read on
+ * the root only (it may be NULL elsewhere); in-place on the root iff sendbuff == recvbuff. ncclBcast is the
+ * legacy in-place form: ncclBroadcast(buff, buff, ...). */
+ncclResult_t ncclBroadcast(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, int root,
+                           ncclComm_t comm, hipStream_t stream);
+ncclResult_t pncclBroadcast(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, int root,
+                            ncclComm_t comm, hipStream_t stream);
+ncclResult_t ncclBcast(void* buff, size_t count, ncclDataType_t datatype, int root, ncclComm_t comm,
+                       hipStream_t stream);
+ncclResult_t pncclBcast(void* buff, size_t count, ncclDataType_t datatype, int root, ncclComm_t comm,
+                        hipStream_t stream);
+
 /* nccl.h.in:496 — in-place iff sendbuff == recvbuff. */
 ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
                            ncclRedOp_t op, ncclComm_t comm, hipStream_t stream);

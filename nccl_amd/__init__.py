@@ -141,6 +141,7 @@ EXPORTED = [
     "ncclReduceScatter", "ncclAllGather", "ncclGroupStart", "ncclGroupEnd",
     "ncclCommRegister", "ncclCommDeregister", "ncclCommWindowRegister", "ncclCommWindowDeregister",
     "ncclWinGetUserPtr", "ncclCommInitRankScalable", "ncclCommMemStats", "ncclGroupSimulateEnd",
+    "ncclBroadcast", "ncclBcast",
 ]
 
 
@@ -190,6 +191,8 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "ncclReduceScatter": (R, [P, P, S, I, I, P, P]),
         "ncclAllGather": (R, [P, P, S, I, P, P]),
         "ncclReduce": (R, [P, P, S, I, I, I, P, P]),
+        "ncclBroadcast": (R, [P, P, S, I, I, P, P]),
+        "ncclBcast": (R, [P, S, I, I, P, P]),
         "ncclGroupStart": (R, []),
         "ncclGroupEnd": (R, []),
         "ncclMemAlloc": (R, [ctypes.POINTER(P), S]),
@@ -460,6 +463,21 @@ class Communicator:
         self.reduce_raw(sendbuf.data_ptr(), _ptr(recvbuf), sendbuf.numel(), torch_dtype_to_nccl(sendbuf.dtype),
                         int(op), root, _stream_ptr(stream, self.device))
 
+    def broadcast(self, sendbuf, recvbuf, root: int = 0, *, stream=None) -> None:
+        """recvbuf on every rank := the root's sendbuf (sendbuf is read on the root only: None elsewhere is fine)."""
+        self._check_tensors("broadcast", sendbuf if self.rank == root else None, recvbuf)
+        if self.rank == root and (sendbuf is None or sendbuf.numel() != recvbuf.numel()
+                                  or sendbuf.dtype != recvbuf.dtype):
+            raise ValueError("broadcast: the root's sendbuf must match recvbuf in dtype and count")
+        self.broadcast_raw(_ptr(sendbuf) if self.rank == root else None, recvbuf.data_ptr(), recvbuf.numel(),
+                           torch_dtype_to_nccl(recvbuf.dtype), root, _stream_ptr(stream, self.device))
+
+    def bcast(self, buf, root: int = 0, *, stream=None) -> None:
+        """In place: buf on every rank := the root's buf (ncclBcast)."""
+        self._check_tensors("bcast", buf)
+        _check(load().ncclBcast(buf.data_ptr(), buf.numel(), torch_dtype_to_nccl(buf.dtype), root, self._comm,
+                                _stream_ptr(stream, self.device)), "ncclBcast")
+
     # ---- collectives on raw device pointers (the C ABI one-to-one) ----
     def all_reduce_raw(self, send: int, recv: int, count: int, dtype: int, op: int, stream: int) -> None:
         _check(load().ncclAllReduce(send, recv, count, dtype, op, self._comm, stream), "ncclAllReduce")
@@ -473,6 +491,9 @@ class Communicator:
     def reduce_raw(self, send: int, recv: Optional[int], count: int, dtype: int, op: int, root: int,
                    stream: int) -> None:
         _check(load().ncclReduce(send, recv, count, dtype, op, root, self._comm, stream), "ncclReduce")
+
+    def broadcast_raw(self, send: Optional[int], recv: int, count: int, dtype: int, root: int, stream: int) -> None:
+        _check(load().ncclBroadcast(send, recv, count, dtype, root, self._comm, stream), "ncclBroadcast")
 
     # ---- registration (nccl.h.in:301-360; nccl4py Communicator.register_buffer / register_window) ----
     def register_buffer(self, ptr: int, size: int) -> int:

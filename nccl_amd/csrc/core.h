@@ -236,7 +236,12 @@ struct RegHandle {  // what ncclCommRegister returns
   RegAlloc* ra;  // nullptr when registration is disabled (NCCL_LOCAL_REGISTER=0)
 };
 
-enum CollFunc { FUNC_ALLREDUCE = 0, FUNC_REDUCESCATTER = 1, FUNC_ALLGATHER = 2, FUNC_REDUCE = 3, FUNC_COUNT = 4 };
+// FUNC_COUNT stays the number of collectives that tests/native/plan_test enumerates by name (its `matrix` mode);
+// FUNC_KINDS sizes the per-collective tables.
+enum CollFunc {
+  FUNC_ALLREDUCE = 0, FUNC_REDUCESCATTER = 1, FUNC_ALLGATHER = 2, FUNC_REDUCE = 3, FUNC_COUNT = 4,
+  FUNC_BROADCAST = 4, FUNC_KINDS = 5
+};
 
 // One collective's NCCL_ALGO / NCCL_PROTO enables (reference: the algoEnable / protoEnable rows of
 // src/graph/tuning.cc:442-462), resolved onto this engine's kernels by loadTuning (enqueue.cc resolveFuncTuning).
@@ -257,7 +262,7 @@ struct CommTuning {
   int protoFlags;           // NCCL_AMD_PROTO_FLAGS | (no release fence before data flags ? 8 : 0) | pulls
   int p2pFence;             // NCCL_AMD_P2P_FENCE: 1 fence, 0 none, -1 unset (none iff all ranks share one GPU)
   int linkChannels;         // channel budget of large plans at n >= 3 (enqueue.cc linkChannelBudget; 0 = none)
-  FuncTuning fn[FUNC_COUNT];  // NCCL_ALGO / NCCL_PROTO per collective (reference grammar, enqueue.cc parseEnableList)
+  FuncTuning fn[FUNC_KINDS];  // NCCL_ALGO / NCCL_PROTO per collective (reference grammar, enqueue.cc parseEnableList)
   int parseError;           // nonzero: NCCL_ALGO / NCCL_PROTO did not parse; every rank's init fails (ncclInvalidUsage)
   int symDisable;          // NCCL_AMD_SYM_DISABLE
   int symOneShot;           // NCCL_AMD_SYM_ONESHOT: caller promises out-of-place window AllReduces

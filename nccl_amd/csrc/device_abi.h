@@ -128,7 +128,7 @@ struct CollBatchArgs {
 // ReduceScatter, AllGather, Reduce) run by ONE launch (reference: ops of a group aggregated into one kernel
 // plan, enqueue.cc:405-470).
 constexpr int kMaxLLBatch = 32;
-enum LLColl { LL_AR = 0, LL_RS = 1, LL_AG = 2, LL_REDUCE = 3 };
+enum LLColl { LL_AR = 0, LL_RS = 1, LL_AG = 2, LL_REDUCE = 3, LL_BCAST = 4 };
 enum LLProto { LLP_LL = 0, LLP_LL64 = 1 };
 constexpr int kLL64Payload = 56;  // payload bytes per 64-byte LL64 line
 struct LLOp {
@@ -140,7 +140,7 @@ struct LLOp {
   int nch;         // channels this op uses
   int chOff;       // first channel (batches spread their ops over the LL channels)
   int coll;        // LLColl
-  int root;        // LL_REDUCE: the rank that folds and stores (the others send and poll only)
+  int root;        // LL_REDUCE: the rank that folds and stores (the others send and poll only); LL_BCAST: the sender
   int proto;       // LLProto: LL (part = 8-byte payloads) or LL64 (part = 64-byte lines of 56 payload bytes)
 };
 // The kernel arguments hold room for K ops: a lone op launches with K = 1 (88 bytes of kernel arguments
@@ -209,6 +209,27 @@ __host__ __device__ inline uint64_t flagIndex(int c, int kind, int from) {
 __host__ __device__ inline uint64_t ctrIndex(int c, int kind, int peer) {
   return ((uint64_t)c * CTR_KINDS + kind) * NCCL_AMD_MAX_RANKS + peer;
 }
+// How a Broadcast's buffer of `count` bytes is cut (kernels.h Channel<.., COLL_BCAST> and llBcastOp; host-callable so
+// that tests/native/bcast_plan_test walks exactly what those kernels walk; the same arithmetic as sliceRange /
+// Channel::blockLen of the other collectives): rank block q holds blockLenOf elements; channel c
+// moves elements [lo, hi) of a block of blockLen elements at pipeline step s; LL channel part j holds payload units
+// [lo, hi) of `units`.
+__host__ __device__ inline uint64_t minU64(uint64_t a, uint64_t b) { return b < a ? b : a; }
+__host__ __device__ inline uint64_t blockLenOf(uint64_t count, uint64_t chunk, int q) {
+  const uint64_t b = (uint64_t)q * chunk;
+  return b >= count ? 0 : minU64(chunk, count - b);
+}
+__host__ __device__ inline void sliceBounds(uint64_t part, uint64_t slice, int c, int s, uint64_t blockLen, uint64_t& lo,
+                                            uint64_t& hi) {
+  const uint64_t pEnd = minU64((uint64_t)(c + 1) * part, blockLen);
+  lo = minU64((uint64_t)c * part + (uint64_t)s * slice, pEnd);
+  hi = minU64(lo + slice, pEnd);
+}
+__host__ __device__ inline void llPartBounds(uint64_t part, int j, uint64_t units, uint64_t& lo, uint64_t& hi) {
+  lo = minU64((uint64_t)j * part, units);
+  hi = minU64(lo + part, units);
+}
+
 // The k-th peer (k = 1 .. n-1) that channel c of rank `me` visits in a workgroup-wide multi-peer loop: the
 // staged scatter's pushes, the pull gather's reads, the zero-copy kernels' reads. Rotated by channel: with one
 // order on every channel, all of a rank's channels would sit on the SAME peer's xGMI link at step position k;

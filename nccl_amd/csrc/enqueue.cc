@@ -96,7 +96,7 @@ const char* const kRefFuncName[kRefFuncs] = {"Broadcast", "Reduce", "AllGather",
 const char* const kAlgoName[kAlgoNames] = {"Tree", "Ring", "CollNetDirect", "CollNetChain", "NVLS", "NVLSTree", "PAT",
                                            "OneShot", "Direct"};
 const char* const kProtoName[kProtoNames] = {"LL", "LL128", "Simple"};
-const int kRefFuncOf[FUNC_COUNT] = {4, 3, 2, 1};  // CollFunc -> the reference's ncclFunc_t row
+const int kRefFuncOf[FUNC_KINDS] = {4, 3, 2, 1, 0};  // CollFunc -> the reference's ncclFunc_t row
 const char* const kForceName[] = {"", "OneShot", "Direct", "Ring", "Tree"};
 
 // the non-empty pieces of s between separators, each with its offset (strtok_r's tokens)
@@ -214,9 +214,9 @@ void loadTuning(CommTuning* t) {
   if (algoStr && parseEnableList("NCCL_ALGO", algoStr, kAlgoName, kAlgoNames, &algoOn[0][0]) != ncclSuccess)
     t->parseError = ncclInvalidUsage;
   const int ll128Default = (int)paramInt("NCCL_AMD_LL128", 0);
-  for (int f = 0; f < FUNC_COUNT; f++) resolveFuncTuning(algoOn[kRefFuncOf[f]], protoOn[kRefFuncOf[f]], ll128Default, &t->fn[f]);
+  for (int f = 0; f < FUNC_KINDS; f++) resolveFuncTuning(algoOn[kRefFuncOf[f]], protoOn[kRefFuncOf[f]], ll128Default, &t->fn[f]);
   if (algoStr || protoStr) {
-    for (int f = 0; f < FUNC_COUNT; f++) {
+    for (int f = 0; f < FUNC_KINDS; f++) {
       const FuncTuning& ft = t->fn[f];
       INFO("NCCL_ALGO / NCCL_PROTO: %s: %s%s, protocols LL %d LL128 %d Simple %d", kRefFuncName[kRefFuncOf[f]],
            ft.noAlgo ? "no algorithm available" : ft.algo != FORCE_NONE ? "forced " : "size table over",
@@ -469,7 +469,9 @@ static ncclResult_t argsCheck(CollInfo* info) {
     return ncclInvalidArgument;
   }
   if (comm->tune.checkPointers && info->count > 0) {
-    NCCLCHECK(ptrCheck(info->sendbuff, comm, "sendbuff", info->opName));
+    // Broadcast reads sendbuff on the root only (reference argcheck.cc:236-238): elsewhere it may be anything
+    if (info->func != FUNC_BROADCAST || comm->rank == info->root)
+      NCCLCHECK(ptrCheck(info->sendbuff, comm, "sendbuff", info->opName));
     if (info->func != FUNC_REDUCE || comm->rank == info->root)
       NCCLCHECK(ptrCheck(info->recvbuff, comm, "recvbuff", info->opName));
   }
@@ -607,7 +609,8 @@ static int tunerRegBuff(ncclComm* comm, const CollInfo& info) {
 // inputs, so it depends only on what all ranks share — count, type, op and the agreed knobs — never on the
 // alignment of this rank's buffers (the kernel loads and stores payloads at any alignment). The blocked
 // collectives need 8-byte multiples as rank blocks (a payload never straddles two blocks) and the line area
-// must hold the payload space: the AllReduce / Reduce buffer or one ReduceScatter / AllGather rank block.
+// must hold the payload space: the AllReduce / Reduce / Broadcast buffer or one ReduceScatter / AllGather rank block
+// (a Broadcast arrives here with its count in bytes: planColl's callers normalised its datatype).
 bool llPlan(const CollInfo& info, LLOp* op) {
   ncclComm* comm = info.comm;
   if (comm->nRanks == 1) return false;
@@ -677,7 +680,7 @@ bool llPlan(const CollInfo& info, LLOp* op) {
   op->nch = nch;
   op->chOff = 0;
   op->coll = info.func == FUNC_ALLREDUCE ? LL_AR : info.func == FUNC_REDUCESCATTER ? LL_RS
-           : info.func == FUNC_ALLGATHER ? LL_AG : LL_REDUCE;
+           : info.func == FUNC_ALLGATHER ? LL_AG : info.func == FUNC_BROADCAST ? LL_BCAST : LL_REDUCE;
   op->root = info.root;
   op->proto = proto;
   return true;
@@ -705,7 +708,7 @@ ncclResult_t planColl(const CollInfo& info, LaunchPlan& p, SymPlan& sp, int* kin
   p.args.comm = comm->devComm;
   p.args.root = info.root;
   const void* argPtr = nullptr;
-  if (info.func != FUNC_ALLGATHER) {
+  if (info.func != FUNC_ALLGATHER && info.func != FUNC_BROADCAST) {
     NCCLCHECK(hostToDevRedOp(comm, info.op, info.datatype, &p.devOp, &p.args.redArg, &argPtr));
     p.args.redArgPtr = argPtr;
   }
@@ -715,7 +718,8 @@ ncclResult_t planColl(const CollInfo& info, LaunchPlan& p, SymPlan& sp, int* kin
   if (n == 1) {
     // reference taskAppend → ncclLaunchOneRank (enqueue.cc:3039-3041, onerank.cu:49-110)
     size_t bytes = info.count * (size_t)ts;
-    if (info.func == FUNC_REDUCE && info.recvbuff == nullptr) {
+    if ((info.func == FUNC_REDUCE && info.recvbuff == nullptr) ||
+        (info.func == FUNC_BROADCAST && info.recvbuff == info.sendbuff)) {  // (an in-place Broadcast: nothing to do)
       *kind = PLAN_NONE;
       return ncclSuccess;
     }
@@ -749,6 +753,7 @@ ncclResult_t planColl(const CollInfo& info, LaunchPlan& p, SymPlan& sp, int* kin
   uint64_t blockElems;
   switch (info.func) {
     case FUNC_ALLREDUCE:
+    case FUNC_BROADCAST:  // (bytes: n blocks of alignUp(divUp(bytes, n), 16), kernels.h Channel::bcastA)
     case FUNC_REDUCE: {
       // rank block = alignUp(divUp(count, n), 16/sizeof(T)) (reference all_reduce.h:38); a Reduce over
       // n >= 3 ranks cuts n-1 blocks, none owned by the root (kernels.h Channel::rootless)
@@ -764,6 +769,8 @@ ncclResult_t planColl(const CollInfo& info, LaunchPlan& p, SymPlan& sp, int* kin
   p.args.count = count;
   p.args.chunk = blockElems;
   uintptr_t bases = (uintptr_t)info.sendbuff | (uintptr_t)info.recvbuff;
+  // (a Broadcast's sendbuff is read on the root only: elsewhere its value says nothing)
+  if (info.func == FUNC_BROADCAST && comm->rank != info.root) bases = (uintptr_t)info.recvbuff;
   bool aligned = (bases & 15) == 0;
   if (info.func == FUNC_REDUCESCATTER || info.func == FUNC_ALLGATHER) aligned = aligned && ((count * ts) & 15) == 0;
   if (comm->tune.forceElementwise) aligned = false;  // diagnostics: T-sized accesses only
@@ -820,7 +827,14 @@ ncclResult_t planColl(const CollInfo& info, LaunchPlan& p, SymPlan& sp, int* kin
   // The reference's own algorithms, forced with NCCL_ALGO=RING / TREE (pipe.h): the ring for AllReduce,
   // ReduceScatter and AllGather, the chain (the intra-node tree) for AllReduce; Reduce's ring is the chain
   // to the root (reduce.h). Where the reference has no such algorithm the default plan runs, with a warning.
-  if (ft.algo == FORCE_RING || ft.algo == FORCE_TREE) {
+  // Broadcast has no fold order for a ring kernel to reproduce: NCCL_ALGO=RING (the reference's only Broadcast
+  // algorithm) and DIRECT run the direct plan; TREE or ONESHOT alone name nothing Broadcast has
+  if (info.func == FUNC_BROADCAST && (ft.algo == FORCE_TREE || ft.algo == FORCE_ONESHOT) &&
+      !(comm->warnedAlgo & (1u << info.func))) {
+    comm->warnedAlgo |= 1u << info.func;
+    WARN("NCCL_ALGO=%s: no such algorithm for Broadcast; using the default plan", kForceName[ft.algo]);
+  }
+  if ((ft.algo == FORCE_RING || ft.algo == FORCE_TREE) && info.func != FUNC_BROADCAST) {
     const bool ring = ft.algo == FORCE_RING;
     int kind = -1;
     if (info.func == FUNC_ALLREDUCE) kind = ring ? PIPE_RING_AR : PIPE_CHAIN_AR;
@@ -885,8 +899,8 @@ ncclResult_t planColl(const CollInfo& info, LaunchPlan& p, SymPlan& sp, int* kin
   // Zero-copy kernels (kernels.h symKernel): buffers in NCCL_WIN_COLL_SYMMETRIC windows (reference: symmetric
   // kernels, src/enqueue.cc ncclSymkAvailable / src/device/symmetric/*), or registered with ncclCommRegister /
   // auto-registered under stream capture (reference: IPC-registered ring buffers, src/register/coll_reg.cc:
-  // 326-395). Reduce keeps the staged path.
-  if (info.func != FUNC_REDUCE && !comm->tune.symDisable) {
+  // 326-395). Reduce and Broadcast keep the staged path whatever their buffers are.
+  if (info.func != FUNC_REDUCE && info.func != FUNC_BROADCAST && !comm->tune.symDisable) {
     size_t sb = count * ts, rb = count * ts;
     if (info.func == FUNC_REDUCESCATTER) sb *= n;
     if (info.func == FUNC_ALLGATHER) rb *= n;
@@ -1087,6 +1101,8 @@ bool batchable(const std::vector<PlannedColl>& run, const PlannedColl& b) {
     return false;
   if (a.p.algo == ALGO_LL) {
     if (run.size() >= (size_t)kMaxLLBatch || a.p.ll.ops[0].proto != b.p.ll.ops[0].proto) return false;
+    // Broadcasts (bytes, any roots) batch with each other only: they run in the byte-typed kernel, which folds nothing
+    if (a.info.func == FUNC_BROADCAST || b.info.func == FUNC_BROADCAST) return a.info.func == b.info.func;
     // AllGather folds nothing: it joins any operator (its own plan carries none)
     if (b.info.func == FUNC_ALLGATHER) return true;
     for (const PlannedColl& x : run)
@@ -1100,7 +1116,7 @@ bool batchable(const std::vector<PlannedColl>& run, const PlannedColl& b) {
   return false;
 }
 
-static const char* const kFuncName[] = {"AllReduce", "ReduceScatter", "AllGather", "Reduce"};
+static const char* const kFuncName[FUNC_KINDS] = {"AllReduce", "ReduceScatter", "AllGather", "Reduce", "Broadcast"};
 
 // One launch for run[0..k) (batchable with each other, in order); the caller forks/joins shared-GPU comms.
 ncclResult_t launchBatch(std::vector<PlannedColl>& run) {
@@ -1295,3 +1311,21 @@ NCCL_EXPORT ncclResult_t ncclReduce(const void* sendbuff, void* recvbuff, size_t
 }
 NCCL_ALIAS(ncclResult_t, ncclReduce, const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, int, ncclComm_t,
            hipStream_t)
+
+// Broadcast (reference collectives.cc:180-207): the payload moves as bytes, the datatype normalised to one byte
+// (reference enqueue.cc:2733-2736), so Broadcasts of any types batch and one byte-typed kernel serves them all.
+// An invalid datatype is left as it is for argsCheck to refuse.
+NCCL_EXPORT ncclResult_t ncclBroadcast(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
+                                       int root, ncclComm_t comm, hipStream_t stream) {
+  const int ts = (int)datatype >= 0 && datatype < ncclNumTypes ? typeSize(datatype) : -1;
+  if (ts > 0) count *= (size_t)ts, datatype = ncclInt8;
+  CollInfo info = {FUNC_BROADCAST, "Broadcast", sendbuff, recvbuff, count, datatype, ncclSum, root, comm, stream};
+  return enqueueCheck(&info);
+}
+NCCL_ALIAS(ncclResult_t, ncclBroadcast, const void*, void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t)
+
+NCCL_EXPORT ncclResult_t ncclBcast(void* buff, size_t count, ncclDataType_t datatype, int root, ncclComm_t comm,
+                                   hipStream_t stream) {
+  return ncclBroadcast(buff, buff, count, datatype, root, comm, stream);
+}
+NCCL_ALIAS(ncclResult_t, ncclBcast, void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t)

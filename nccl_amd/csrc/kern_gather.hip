@@ -2,6 +2,7 @@
 #include "kernels.h"
 namespace ncclamd {
 ncclResult_t launchKernGather(const LaunchPlan& p) {
+  if (p.func == FUNC_BROADCAST) return launchBcast<>(p);
   switch (p.eltSize) {
     case 1: return launchTyped<uint8_t, 0>(p);
     case 2: return launchTyped<uint16_t, 0>(p);

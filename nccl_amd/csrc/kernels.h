@@ -646,7 +646,9 @@ __device__ __forceinline__ void foldRange(const Red<T, OP>& fn, int n, const cha
 // instead of 2(n-1)/n*S). Same fold order as the two-shot path, so results are identical.
 // COLL_ARREF = the direct AllReduce on the reference's ring partition (NCCL_AMD_REF_ORDER, Channel::refPart): its
 // own instantiation, so the default AllReduce kernel carries none of its indexing.
-enum Coll { COLL_AR = 0, COLL_RS = 1, COLL_AG = 2, COLL_REDUCE = 3, COLL_AR1 = 4, COLL_ARREF = 5 };
+// COLL_BCAST = Broadcast: the root scatters block p to owner p, the owners publish for the mesh gather (bcastA /
+// bcastB below; byte-typed, instantiated in kern_gather.hip only).
+enum Coll { COLL_AR = 0, COLL_RS = 1, COLL_AG = 2, COLL_REDUCE = 3, COLL_AR1 = 4, COLL_ARREF = 5, COLL_BCAST = 6 };
 
 // Element range [lo,hi) of a block handled by channel c at pipeline step s (offsets inside the block).
 __device__ __forceinline__ void sliceRange(const CollArgs& a, int c, int s, uint64_t blockLen, uint64_t& lo,
@@ -702,6 +704,9 @@ struct Channel {
   static constexpr bool kAR = COLL == COLL_AR || COLL == COLL_ARREF;
 
   __device__ uint64_t blockLen(int q) const {
+    // Broadcast cuts its buffer with the host-callable functions of device_abi.h (blockLenOf / sliceBounds, the same
+    // arithmetic), which tests/native/bcast_plan_test walks on the CPU
+    if constexpr (COLL == COLL_BCAST) return blockLenOf(a.count, a.chunk, q);
     if (kAR || COLL == COLL_REDUCE) {
       uint64_t b = (uint64_t)q * a.chunk;
       return b >= a.count ? 0 : min(a.chunk, a.count - b);
@@ -752,6 +757,12 @@ struct Channel {
   // Block b's slice at pipeline step `step`: elements [off, off + len) of the buffer.
   __device__ void blockSlice(int step, int b, uint64_t& off, uint64_t& len) const {
     uint64_t lo, hi;
+    if constexpr (COLL == COLL_BCAST) {
+      sliceBounds(a.part, a.slice, cl, step, blockLen(b), lo, hi);
+      off = (uint64_t)b * a.chunk + lo;
+      len = hi - lo;
+      return;
+    }
     if (!refPart()) {
       sliceRange(a, cl, step, blockLen(b), lo, hi);
       off = (uint64_t)b * a.chunk + lo;
@@ -1004,6 +1015,127 @@ struct Channel {
     __syncthreads();
     return true;
   }
+
+  // ---- Broadcast (COLL_BCAST; T is a byte). The buffer is cut into n rank blocks like an AllReduce's. The root
+  // scatters block p to owner p over the RS credits of the pair (root, p) alone (bcastA); owner p copies its slice
+  // out of staging into its output and publishes it for the gather (bcastB; the root publishes its own block
+  // straight from its input); every non-root then gathers the other n-1 blocks with phaseC. Per link: S/n out of
+  // the root, S/n between every other pair. NCCL_AMD_RS_PULL is not applied: the scatter always pushes into the
+  // owner's slab, under the pair's own slot and credit sequence, which is all any other collective relies on.
+  // Gather sequences: under the pull gather every rank publishes once per step and every rank — the root too,
+  // which reads nothing (bcastRootC) — waits for and acks every peer's publication, so the channel's publication
+  // sequence advances as in an AllGather; under the push gather the owners do not push to the root and the pair
+  // counters (owner, root) stay put on both sides, as they do for the non-root pairs of a Reduce.
+
+  // A (root): block p's slice to owner p's RS staging; out of place, the same read also fills my output
+  __device__ bool bcastA(int step) {
+    int tid = threadIdx.x;
+    if (tid < NCCL_AMD_MAX_RANKS) {
+      uint64_t s = ctr(CTR_SEND_RS, tid);
+      sh.want[tid] = (tid < n && tid != me && s + 1 > (uint64_t)nSlots) ? s + 1 - nSlots : 0;
+    }
+    if (tid == 0)
+      for (int k = 1; k < n; k++) {
+        const int p = peerAt(k);
+        sh.pushPtr[k - 1] = dc.staging[p] + stagingOffset(dc, c, STG_RS, (int)(ctr(CTR_SEND_RS, p) % nSlots), me);
+      }
+    __syncthreads();
+    if (!waitAll(dc, sh.st, myFlags(FLG_RS_ACK), sh.want, forceAcq)) return false;
+    const bool outOfPlace = a.recvbuff != a.sendbuff;
+    for (int k = 1; k < n; k++) {
+      uint64_t off, len;
+      blockSlice(step, peerAt(k), off, len);
+      const char* src = (const char*)a.sendbuff + off * ts;
+      copyRangeMulti<T>(outOfPlace ? (char*)a.recvbuff + off * ts : nullptr, sh.pushPtr + (k - 1), 1, src, len * ts, aligned);
+    }
+    if (tid < NCCL_AMD_MAX_RANKS) {
+      bool act = tid < n && tid != me;
+      sh.sigVal[tid] = act ? ctr(CTR_SEND_RS, tid) + 1 : 0;
+      sh.sigPtr[tid] = act ? dc.flags[tid] + flagIndex(c, FLG_RS_READY, me) : nullptr;
+    }
+    __syncthreads();
+    signalAll(sh.sigPtr, sh.sigVal, NCCL_AMD_MAX_RANKS, !noRel);
+    if (tid < n && tid != me) ctr(CTR_SEND_RS, tid)++;
+    __syncthreads();
+    return true;
+  }
+
+  // B: publish my block's slice for the gather — an owner from the root's slice in its staging (which it also
+  // copies into its output and acks to the root), the root from its input
+  __device__ bool bcastB(int step) {
+    int tid = threadIdx.x;
+    const int root = a.root;
+    if (!isRoot) {
+      if (tid < NCCL_AMD_MAX_RANKS) sh.want[tid] = tid == root ? ctr(CTR_RECV_RS, tid) + 1 : 0;
+      __syncthreads();
+      if (!waitAll<PROBE_STAGED>(dc, sh.st, myFlags(FLG_RS_READY), sh.want, !noAcq, &sh.probe)) return false;
+    }
+    if (tid < NCCL_AMD_MAX_RANKS) {
+      uint64_t s = agPull ? ctr(CTR_PULL_PUB, 0) : ctr(CTR_SEND_AG, tid);
+      bool dstPeer = tid < n && tid != me && (agPull || tid != root);
+      sh.want[tid] = (dstPeer && s + 1 > (uint64_t)nSlots) ? s + 1 - nSlots : 0;
+    }
+    __syncthreads();
+    if (!waitAll(dc, sh.st, myFlags(agPull ? FLG_PULL_ACK : FLG_AG_ACK), sh.want, forceAcq)) return false;
+    uint64_t lo, hi;
+    sliceBounds(a.part, a.slice, cl, step, blockLen(me), lo, hi);
+    const uint64_t myOff = (uint64_t)me * a.chunk + lo, nelem = hi - lo;
+    if (tid == 0) {
+      int np = 0;
+      if (agPull) {
+        sh.pushPtr[np++] = dc.staging[me] + stagingOffset(dc, c, STG_AG, (int)(ctr(CTR_PULL_PUB, 0) % nSlots), me);
+      } else {
+        for (int k = 1; k < n; k++) {
+          int p = (me + k) % n;
+          if (p != root)
+            sh.pushPtr[np++] = dc.staging[p] + stagingOffset(dc, c, STG_AG, (int)(ctr(CTR_SEND_AG, p) % nSlots), me);
+        }
+      }
+      sh.nPush = np;
+      sh.srcPtr[0] = isRoot ? (const char*)a.sendbuff + myOff * ts
+                            : dc.staging[me] + stagingOffset(dc, c, STG_RS, (int)(ctr(CTR_RECV_RS, root) % nSlots), root);
+    }
+    __syncthreads();
+    char* dstLocal = (char*)a.recvbuff + myOff * ts;
+    if (isRoot && a.recvbuff == a.sendbuff) dstLocal = nullptr;
+    copyRangeMulti<T>(dstLocal, sh.pushPtr, sh.nPush, sh.srcPtr[0], nelem * ts, aligned);
+    if (tid < NCCL_AMD_MAX_RANKS) {
+      bool dstPeer = tid < n && tid != me && (agPull || tid != root);
+      sh.sigVal[tid] = dstPeer ? (agPull ? ctr(CTR_PULL_PUB, 0) : ctr(CTR_SEND_AG, tid)) + 1 : 0;
+      sh.sigPtr[tid] = dstPeer ? dc.flags[tid] + flagIndex(c, agPull ? FLG_PULL_READY : FLG_AG_READY, me) : nullptr;
+      bool ack = !isRoot && tid == root;
+      sh.sigVal[NCCL_AMD_MAX_RANKS + tid] = ack ? ctr(CTR_RECV_RS, tid) + 1 : 0;
+      sh.sigPtr[NCCL_AMD_MAX_RANKS + tid] = ack ? dc.flags[tid] + flagIndex(c, FLG_RS_ACK, me) : nullptr;
+    }
+    __syncthreads();
+    signalAll(sh.sigPtr, sh.sigVal, 2 * NCCL_AMD_MAX_RANKS, !noRel || forceRel);
+    if (tid < n && tid != me) {
+      if (!isRoot && tid == root) ctr(CTR_RECV_RS, tid)++;
+      if (!agPull && tid != root) ctr(CTR_SEND_AG, tid)++;
+    }
+    if (agPull && tid == 0) ctr(CTR_PULL_PUB, 0)++;
+    __syncthreads();
+    return true;
+  }
+
+  // C at the root under the pull gather: it reads no block, but stays in the channel's publication sequence —
+  // waits for every peer's publication of this step and acks it (the owner frees that slot on EVERY peer's ack)
+  __device__ bool bcastRootC(int step) {
+    int tid = threadIdx.x;
+    if (tid < NCCL_AMD_MAX_RANKS) sh.want[tid] = (tid < n && tid != me) ? ctr(CTR_PULL_GOT, tid) + 1 : 0;
+    __syncthreads();
+    if (!waitAll<PROBE_STAGED>(dc, sh.st, myFlags(FLG_PULL_READY), sh.want, false, &sh.probe)) return false;
+    if (tid < NCCL_AMD_MAX_RANKS) {
+      bool peer = tid < n && tid != me;
+      sh.sigVal[tid] = peer ? ctr(CTR_PULL_GOT, tid) + 1 : 0;
+      sh.sigPtr[tid] = peer ? dc.flags[tid] + flagIndex(c, FLG_PULL_ACK, me) : nullptr;
+    }
+    __syncthreads();
+    signalAll(sh.sigPtr, sh.sigVal, NCCL_AMD_MAX_RANKS, forceRel);  // credits only
+    if (tid < n && tid != me) ctr(CTR_PULL_GOT, tid)++;
+    __syncthreads();
+    return true;
+  }
 };
 
 // Per-channel credit counters live in device memory between launches; a workgroup keeps them in LDS.
@@ -1047,13 +1179,27 @@ __device__ __forceinline__ bool runChannel(const CollArgs& a, const DevComm& dc,
   // (NCCL_AMD_AG_PULL=1), 32 = RS pull (NCCL_AMD_RS_PULL=1), 64 = no acquire after data waits (diagnostics
   // only: measures the acquire's cost)
   Channel<T, OP, COLL> ch{a, dc, sh, fn, c, dc.rank, dc.nRanks, dc.nSlots, a.aligned != 0,
-                          (COLL != COLL_REDUCE) || dc.rank == a.root, (a.protoFlags & 1) != 0,
+                          (COLL != COLL_REDUCE && COLL != COLL_BCAST) || dc.rank == a.root, (a.protoFlags & 1) != 0,
                           (a.protoFlags & 2) != 0, (a.protoFlags & 8) != 0, (a.protoFlags & 64) != 0,
-                          (COLL == COLL_AR || COLL == COLL_ARREF || COLL == COLL_AG) && (a.protoFlags & 16) != 0,
+                          (COLL == COLL_AR || COLL == COLL_ARREF || COLL == COLL_AG || COLL == COLL_BCAST) &&
+                              (a.protoFlags & 16) != 0,
                           (COLL == COLL_AR || COLL == COLL_ARREF || COLL == COLL_RS) && (a.protoFlags & 32) != 0, cl};
   if (COLL == COLL_AR1) {
     bool ok = true;
     for (int s = 0; ok && s < a.nSteps; s++) ok = ch.oneShotA(s) && ch.oneShotB(s);
+    return ok;
+  }
+  if constexpr (COLL == COLL_BCAST) {
+    // A(0); for s: B(s); A(s+1); C(s) — the root runs A and, under the pull gather, the ack-only C; the others run
+    // B and the gather of the staged AllReduce / AllGather (phaseC)
+    const bool root = ch.isRoot;
+    bool ok = !root || a.nSteps == 0 || ch.bcastA(0);
+    for (int s = 0; ok && s < a.nSteps; s++) {
+      ok = ch.bcastB(s);
+      if (ok && root && s + 1 < a.nSteps) ok = ch.bcastA(s + 1);
+      if (ok && !root) ok = ch.phaseC(s);
+      else if (ok && ch.agPull) ok = ch.bcastRootC(s);
+    }
     return ok;
   }
   constexpr bool hasA = COLL != COLL_AG;
@@ -1496,6 +1642,174 @@ __device__ __forceinline__ bool ll64ChannelOp(const DevComm& dc, const Red<T, OP
   return ok && !abortSh;
 }
 
+// LL / LL64 Broadcast (LL_BCAST; byte-typed). Payload space: the whole buffer. The root stores its part's payload
+// lines into every peer's line area and, out of place, copies the part into its own output; a non-root polls the
+// root's lines and places the payloads. That alone would break the parity double-buffering (see above: a rank may
+// reach epoch e+2 on a channel only after it has received every peer's e+1 lines), so every non-root also stores ONE
+// token line — the part's first line, payload ignored — into every peer's area, the root's included, and every rank
+// polls that line of every non-root peer before its epoch advances: n-1 extra lines per rank and part instead of the
+// n x payload traffic of "everyone sends to everyone". The host plan leaves no channel of the op without a payload
+// (llPlan), so every rank takes part on every channel the op uses.
+// One line of `p` polled until both halves (LL) / the flag lane (LL64: p points at the line's last 16 bytes) show
+// this epoch's flag; false on abort / timeout.
+__device__ __forceinline__ bool llPollLine(const DevComm& dc, const char* p, uint32_t flag, bool ll64, uint64_t t0,
+                                           int& abortSh, u32x4& v) {
+  uint32_t spins = 0;
+  while (true) {
+    v = loadLine16(p);
+    if ((ll64 || v.y == flag) && (ll64 ? v.z == flag : true) && v.w == flag) return true;
+    __builtin_amdgcn_s_sleep(1);
+    if ((++spins & 1023) == 0) {
+      if (__hip_atomic_load(dc.abortFlag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) {
+        reportError(dc, DERR_ABORT);
+        abortSh = 1;
+      } else if (__hip_atomic_load(dc.errorWord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) ||
+                 clockTicks() - t0 > dc.timeoutTicks) {
+        reportError(dc, DERR_TIMEOUT);
+        abortSh = 1;
+      }
+      if (abortSh) return false;
+    }
+  }
+}
+// 8 bytes of a user buffer of nbytes at any alignment (0 past the end) / stored back (nothing past the end)
+__device__ __forceinline__ uint64_t llLoad8(const char* base, uint64_t pk, uint64_t nbytes) {
+  const char* p = base + pk * 8;
+  const uintptr_t al = (uintptr_t)p;
+  uint64_t v = 0;
+  if (pk * 8 + 8 <= nbytes) {
+    if ((al & 7) == 0) v = *(const uint64_t*)p;
+    else if ((al & 3) == 0) v = ((const uint32_t*)p)[0] | ((uint64_t)((const uint32_t*)p)[1] << 32);
+    else for (int b = 0; b < 8; b++) v |= (uint64_t)(unsigned char)p[b] << (8 * b);
+  } else {
+    for (uint64_t b = pk * 8; b < nbytes; b++) v |= (uint64_t)(unsigned char)base[b] << (8 * (b - pk * 8));
+  }
+  return v;
+}
+__device__ __forceinline__ void llStore8(char* base, uint64_t pk, uint64_t nbytes, uint64_t v) {
+  char* p = base + pk * 8;
+  const uintptr_t al = (uintptr_t)p;
+  if (pk * 8 + 8 <= nbytes) {
+    if ((al & 7) == 0) {
+      *(uint64_t*)p = v;
+    } else if ((al & 3) == 0) {
+      ((uint32_t*)p)[0] = (uint32_t)v;
+      ((uint32_t*)p)[1] = (uint32_t)(v >> 32);
+    } else {
+      for (int b = 0; b < 8; b++) p[b] = (char)(v >> (8 * b));
+    }
+  } else {
+    for (uint64_t b = pk * 8; b < nbytes; b++) base[b] = (char)(v >> (8 * (b - pk * 8)));
+  }
+}
+
+template <int P>
+__device__ __forceinline__ bool llBcastOp(const DevComm& dc, const LLOp& op, int c, int j, uint64_t e64, int& abortSh) {
+  const int tid = threadIdx.x, me = dc.rank, n = dc.nRanks, root = op.root;
+  const uint32_t flag = (uint32_t)e64 ? (uint32_t)e64 : 1u;
+  const int par = (int)(e64 & 1);
+  const uint64_t nbytes = op.count;  // bytes (the datatype was normalised)
+  const char* send = (const char*)op.send;
+  char* recv = (char*)op.recv;
+  const char* myLL = (const char*)dc.flags[me];
+  bool ok = true;
+  if constexpr (P == LLP_LL) {
+    const uint64_t npk = (nbytes + 7) / 8;
+    uint64_t lo, hi;
+    llPartBounds(op.part, j, npk, lo, hi);
+    if (me == root) {
+      for (uint64_t i = lo + tid; i < hi; i += kThreads) {
+        const uint64_t v = llLoad8(send, i, nbytes);
+        const u32x4 line = {(uint32_t)v, flag, (uint32_t)(v >> 32), flag};
+        for (int k = 1; k < n; k++) storeRemote((char*)dc.flags[(me + k) % n] + llLineOffset(dc, c, par, me) + (i - lo) * 16, line);
+        if (recv != send) llStore8(recv, i, nbytes, v);
+      }
+    } else if (tid < n && tid != me) {  // my token: the part's first line in every peer's area
+      storeRemote((char*)dc.flags[tid] + llLineOffset(dc, c, par, me), u32x4{0u, flag, 0u, flag});
+    }
+    __syncthreads();
+    const uint64_t t0 = clockTicks();
+    u32x4 v;
+    if (tid < n && tid != me && tid != root) ok = llPollLine(dc, myLL + llLineOffset(dc, c, par, tid), flag, false, t0, abortSh, v);
+    if (me != root) {
+      for (uint64_t pk = lo + tid; ok && pk < hi; pk += kThreads) {
+        ok = llPollLine(dc, myLL + llLineOffset(dc, c, par, root) + (pk - lo) * 16, flag, false, t0, abortSh, v);
+        if (ok) llStore8(recv, pk, nbytes, llPayload(v));  // both halves matched in this one load
+      }
+    }
+  } else {
+    const int lane = tid & 63, u = tid & 3;
+    constexpr uint32_t kUnits = kLL64Payload / 8;
+    const uint32_t nLines = (uint32_t)((nbytes + kLL64Payload - 1) / kLL64Payload);
+    uint64_t lo64, hi64;
+    llPartBounds(op.part, j, nLines, lo64, hi64);
+    const uint32_t lo = (uint32_t)lo64, hi = (uint32_t)hi64;  // (an op's lines fit the line area: far below 2^32)
+    const uint64_t flag64 = ((uint64_t)flag << 32) | flag;
+    if (me == root) {
+      for (uint32_t i = lo * 4 + tid; i < hi * 4; i += kThreads) {
+        const uint32_t pk = (i >> 2) * kUnits + 2 * u;
+        const uint64_t v0 = llLoad8(send, pk, nbytes), v1 = u < 3 ? llLoad8(send, pk + 1, nbytes) : flag64;
+        const u32x4 unit = {(uint32_t)v0, (uint32_t)(v0 >> 32), (uint32_t)v1, (uint32_t)(v1 >> 32)};
+        for (int k = 1; k < n; k++)
+          storeRemote((char*)dc.flags[(me + k) % n] + ll64LineOffset(dc, c, par, me) + (i - lo * 4) * 16, unit);
+        if (recv != send) {
+          if ((uint64_t)pk * 8 < nbytes) llStore8(recv, pk, nbytes, v0);
+          if (u < 3 && (uint64_t)(pk + 1) * 8 < nbytes) llStore8(recv, pk + 1, nbytes, v1);
+        }
+      }
+    } else if (tid < 4 * n && (tid >> 2) != me) {  // my token line: 4 consecutive lanes, one 64-byte segment
+      const uint64_t hiHalf = u == 3 ? flag64 : 0;
+      storeRemote((char*)dc.flags[tid >> 2] + ll64LineOffset(dc, c, par, me) + u * 16,
+                  u32x4{0u, 0u, (uint32_t)hiHalf, (uint32_t)(hiHalf >> 32)});
+    }
+    __syncthreads();
+    const uint64_t t0 = clockTicks();
+    u32x4 v;
+    if (tid < n && tid != me && tid != root) ok = llPollLine(dc, myLL + ll64LineOffset(dc, c, par, tid) + 48, flag, true, t0, abortSh, v);
+    if (me != root) {
+      // as ll64ChannelOp: a line is accepted once its flag lane (u == 3) sees the flag; whole 4-lane groups
+      const char* rootLL = myLL + ll64LineOffset(dc, c, par, root);
+      for (uint32_t i = lo * 4 + tid; ok && i < hi * 4; i += kThreads) {
+        const uint32_t off = (i - lo * 4) * 16;
+        bool pending = true;
+        uint32_t spins = 0;
+        while (true) {
+          bool mineOk = true;
+          if (pending) {
+            v = loadLine16(rootLL + off);
+            mineOk = u != 3 || (v.z == flag && v.w == flag);
+          }
+          const bool lineOk = __shfl((int)mineOk, (lane & ~3) | 3) != 0;
+          if (pending && lineOk) pending = false;
+          if (!__any(pending)) break;
+          __builtin_amdgcn_s_sleep(1);
+          if ((++spins & 1023) == 0) {
+            if (__hip_atomic_load(dc.abortFlag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) {
+              reportError(dc, DERR_ABORT);
+              abortSh = 1;
+            } else if (__hip_atomic_load(dc.errorWord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) ||
+                       clockTicks() - t0 > dc.timeoutTicks) {
+              reportError(dc, DERR_TIMEOUT);
+              abortSh = 1;
+            }
+            if (abortSh) break;
+          }
+        }
+        if (pending) ok = false;
+      }
+      __atomic_signal_fence(__ATOMIC_SEQ_CST);  // the re-reads below stay behind the polls
+      for (uint32_t i = lo * 4 + tid; ok && i < hi * 4; i += kThreads) {
+        const uint32_t pk = (i >> 2) * kUnits + 2 * u;
+        v = loadSeenLine16(rootLL + (i - lo * 4) * 16);
+        if ((uint64_t)pk * 8 < nbytes) llStore8(recv, pk, nbytes, v.x | ((uint64_t)v.y << 32));
+        if (u < 3 && (uint64_t)(pk + 1) * 8 < nbytes) llStore8(recv, pk + 1, nbytes, v.z | ((uint64_t)v.w << 32));
+      }
+    }
+  }
+  __syncthreads();  // every payload of this op is placed before the next op's lines go out
+  return ok && !abortSh;
+}
+
 // One launch runs a batch of LL ops (a single ReduceScatter / AllGather, or up to 32 AllReduces); op k occupies channels [chOff_k, chOff_k + nch_k) mod
 // llChannels, so the small ops of a batch land on different channels and run in parallel (one
 // round trip for the batch). A channel runs its ops in batch order and its epoch advances once per op
@@ -1530,6 +1844,13 @@ __global__ void __launch_bounds__(kThreads) kCoResident llKernel(LLArgs<K> a) {
     if (j >= o.nch) break;                // (a lone op's grid is its channel count; a batch's masks say so)
     e64++;
     // one protocol per launch (a batch holds ops of one protocol): each kernel keeps its own register budget
+    // Broadcast ops run only in the byte-typed kernel (launchBcast): no other instantiation carries the code
+    if constexpr (std::is_same<T, uint8_t>::value && OP == 0) {
+      if (o.coll == LL_BCAST) {
+        if (!llBcastOp<P>(dc, o, c, j, e64, abortSh)) break;
+        continue;
+      }
+    }
     const bool ok = P == LLP_LL64 ? ll64ChannelOp<T, OP>(dc, fn, o, c, j, e64, abortSh)
                                   : llChannelOp<T, OP>(dc, fn, o, c, j, e64, abortSh);
     if (!ok) break;
@@ -1830,6 +2151,18 @@ inline void launchColl(const LaunchPlan& p) {
     }
   }
   NCCL_AMD_LAUNCH((collKernel<T, OP, COLL>), dim3(p.nChannels), dim3(kThreads), 0, p.stream, p.args);
+}
+
+// Broadcast: bytes, whatever the user's datatype (a template only so that the one unit that calls it, kern_gather.hip,
+// instantiates its kernels)
+template <typename T = uint8_t>
+inline ncclResult_t launchBcast(const LaunchPlan& p) {
+  static_assert(sizeof(T) == 1, "Broadcast moves bytes");
+  if (p.algo == ALGO_LL) launchLL<T, 0>(p);
+  else if (p.algo == ALGO_DIRECT) launchColl<T, 0, COLL_BCAST>(p);
+  else return ncclInternalError;
+  HIPCHECK(hipGetLastError());
+  return ncclSuccess;
 }
 
 template <typename T, int OP>

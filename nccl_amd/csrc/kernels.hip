@@ -204,7 +204,7 @@ ncclResult_t launchMapCheck(const DevComm* dc, const MapCheckArgs& a, uint64_t* 
 ncclResult_t launchPlan(const LaunchPlan& p) {
   if (p.algo == ALGO_COPY)
     return launchCopy(p.args.recvbuff, p.args.sendbuff, p.bytes, p.stream, p.copyVariant, p.copyGrid, p.copyXcdShift);
-  if (p.func == FUNC_ALLGATHER) return launchKernGather(p);
+  if (p.func == FUNC_ALLGATHER || p.func == FUNC_BROADCAST) return launchKernGather(p);  // the byte-typed unit
   switch (p.datatype) {
     case ncclInt8: case ncclUint8: return launchKernU8(p);
     case ncclInt32: case ncclUint32: return launchKernU32(p);

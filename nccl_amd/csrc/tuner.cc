@@ -8,7 +8,7 @@
 //
 // Mapping onto this engine (one xGMI node): for AllReduce, (TREE|RING, LL) → the LL
 // kernel, (TREE, SIMPLE) → one-shot, (RING, SIMPLE) → direct scatter-reduce-gather; for ReduceScatter,
-// AllGather and Reduce only (RING, SIMPLE) exists. Every other entry is NCCL_ALGO_PROTO_IGNORE. A plugin
+// AllGather, Reduce and Broadcast (RING, SIMPLE) is the direct kernel, (RING, LL) the LL and (RING, LL128) the LL64 one. Every other entry is NCCL_ALGO_PROTO_IGNORE. A plugin
 // that leaves the table unchanged keeps the engine's own size table; nChannels > 0 overrides the channel
 // count (clamped to what the chosen kernel supports).
 #include <dlfcn.h>
@@ -144,16 +144,16 @@ ModelCost modelCost(ModelAlgo a, CollFunc func, int n, size_t bytes) {
   const double oneShotHbm = std::min(hbm, 32 * 5.0e4);  // 32 channels x ≈50 GB/s per workgroup
   if (n <= 1) return {2.0, (a == MODEL_COPY ? 2.0 * S : 0.0) / hbm};  // one rank: a copy or nothing
   const double nl = n - 1.0;
-  const bool ar = func == FUNC_ALLREDUCE, red = func == FUNC_REDUCE;
+  const bool ar = func == FUNC_ALLREDUCE, red = func == FUNC_REDUCE, bc = func == FUNC_BROADCAST;
   double lat = 10.0, linkB = 0, hbmB = 0, links = nl;
   switch (a) {
-    case MODEL_LL:  // 16-byte lines carry 8 payload bytes, to every peer for AllReduce / Reduce
+    case MODEL_LL:  // 16-byte lines carry 8 payload bytes, to every peer for AllReduce / Reduce (Broadcast: the root's)
       lat = 4.0;
-      linkB = (ar || red ? 2.0 * nl : 2.0 * nl / n) * S;
+      linkB = (ar || red || bc ? 2.0 * nl : 2.0 * nl / n) * S;
       break;
     case MODEL_LL128:  // 64-byte lines carry 56 payload bytes
       lat = 4.5;
-      linkB = (64.0 / 56.0) * (ar || red ? nl : nl / n) * S;
+      linkB = (64.0 / 56.0) * (ar || red || bc ? nl : nl / n) * S;
       break;
     case MODEL_ONESHOT:  // every rank publishes its buffer to every peer and folds all n
       lat = 7.0;
@@ -165,6 +165,10 @@ ModelCost modelCost(ModelAlgo a, CollFunc func, int n, size_t bytes) {
       lat = a == MODEL_SYM ? 8.0 : 10.0;
       linkB = (ar ? 2.0 * nl / n : nl / n) * S;
       hbmB = ar ? (2.0 + 4.0 * nl / n) * S : 2.0 * S;
+      // Broadcast: S / n per link out of the root and between every other pair; an owner's HBM sees its block 4 times
+      // (staged in, read, written to the output and to its gather slot), the slot's n - 2 readers and the other
+      // n - 1 blocks written: (2 + 1 / n) S
+      if (bc) hbmB = (2.0 + 1.0 / n) * S;
       break;
     case MODEL_RING:  // one link per direction; n-1 (RS / AG) or 2(n-1) (AllReduce) pipelined hops
       lat = 10.0 + 2.0 * (ar ? 2.0 * nl : nl);
@@ -206,7 +210,8 @@ void tunerPick(ncclComm* comm, CollFunc func, size_t bytes, int numPipeOps, int 
     table[NCCL_ALGO_TREE][NCCL_PROTO_SIMPLE] = us(MODEL_ONESHOT);
     table[NCCL_ALGO_RING][NCCL_PROTO_SIMPLE] = us(MODEL_DIRECT);
   } else {
-    f = func == FUNC_REDUCESCATTER ? ncclFuncReduceScatter : func == FUNC_ALLGATHER ? ncclFuncAllGather : ncclFuncReduce;
+    f = func == FUNC_REDUCESCATTER ? ncclFuncReduceScatter : func == FUNC_ALLGATHER ? ncclFuncAllGather
+      : func == FUNC_BROADCAST ? ncclFuncBroadcast : ncclFuncReduce;
     table[NCCL_ALGO_RING][NCCL_PROTO_SIMPLE] = us(MODEL_DIRECT);
     if (llOk) table[NCCL_ALGO_RING][NCCL_PROTO_LL] = us(MODEL_LL);
     if (ll128Ok) table[NCCL_ALGO_RING][NCCL_PROTO_LL128] = us(MODEL_LL128);
