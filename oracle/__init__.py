@@ -75,13 +75,17 @@ def dev_op(op: int, dtype: int, nranks: int):
     return d.value, arg.value
 
 
+def _dev_op_or_premul(op: int, dtype: int, n: int, premul_scalar_bits: int | None):
+    """(devop, arg) of `op`, or of a user PreMulSum operator whose scalar has the storage bits `premul_scalar_bits`."""
+    if premul_scalar_bits is not None:
+        return DEV_PREMULSUM, int(premul_scalar_bits)
+    return dev_op(op, dtype, n)
+
+
 def all_reduce(inputs: Sequence[np.ndarray], dtype: int, op: int = 0, premul_scalar_bits: int | None = None):
     """Result of ncclAllReduce over `inputs` (one array per rank, storage dtype NP_STORAGE[dtype])."""
     n = len(inputs)
-    if premul_scalar_bits is not None:
-        d, arg = DEV_PREMULSUM, premul_scalar_bits
-    else:
-        d, arg = dev_op(op, dtype, n)
+    d, arg = _dev_op_or_premul(op, dtype, n, premul_scalar_bits)
     ins = [np.ascontiguousarray(x) for x in inputs]
     out = np.empty_like(ins[0])
     rc = lib().oracle_all_reduce(dtype, d, arg, n, _ptrs(ins), ins[0].size, out.ctypes.data)
@@ -89,10 +93,10 @@ def all_reduce(inputs: Sequence[np.ndarray], dtype: int, op: int = 0, premul_sca
     return out
 
 
-def all_reduce_chain(inputs: Sequence[np.ndarray], dtype: int, op: int = 0):
+def all_reduce_chain(inputs: Sequence[np.ndarray], dtype: int, op: int = 0, premul_scalar_bits: int | None = None):
     """ncclAllReduce with NCCL_ALGO=TREE on one node: the chain 0 <- 1 <- ... <- n-1 (fold order n-1 .. 0)."""
     n = len(inputs)
-    d, arg = dev_op(op, dtype, n)
+    d, arg = _dev_op_or_premul(op, dtype, n, premul_scalar_bits)
     ins = [np.ascontiguousarray(x) for x in inputs]
     out = np.empty_like(ins[0])
     rc = lib().oracle_all_reduce_chain(dtype, d, arg, n, _ptrs(ins), ins[0].size, out.ctypes.data)
@@ -116,12 +120,12 @@ def ring_nccl_plan(count: int, type_size: int, nranks: int, nchannels: int, buff
 
 
 def all_reduce_ring_nccl(inputs: Sequence[np.ndarray], dtype: int, op: int, nchannels: int, buffsize: int = 0,
-                         proto: int = PROTO_SIMPLE):
+                         proto: int = PROTO_SIMPLE, premul_scalar_bits: int | None = None):
     """ncclAllReduce with NCCL_ALGO=RING in the reference's full-size order for protocol `proto` (Simple by
     default): channel parts, loops of n chunks, last loop re-cut (all_reduce.h:21-81) on a communicator of
     `nchannels` channels."""
     n = len(inputs)
-    d, arg = dev_op(op, dtype, n)
+    d, arg = _dev_op_or_premul(op, dtype, n, premul_scalar_bits)
     ins = [np.ascontiguousarray(x) for x in inputs]
     out = np.empty_like(ins[0])
     rc = lib().oracle_all_reduce_ring_nccl_proto(dtype, d, arg, n, _ptrs(ins), ins[0].size, out.ctypes.data,
@@ -132,10 +136,7 @@ def all_reduce_ring_nccl(inputs: Sequence[np.ndarray], dtype: int, op: int, ncha
 
 def reduce_scatter(inputs: Sequence[np.ndarray], dtype: int, op: int = 0, premul_scalar_bits: int | None = None):
     n = len(inputs)
-    if premul_scalar_bits is not None:
-        d, arg = DEV_PREMULSUM, premul_scalar_bits
-    else:
-        d, arg = dev_op(op, dtype, n)
+    d, arg = _dev_op_or_premul(op, dtype, n, premul_scalar_bits)
     ins = [np.ascontiguousarray(x) for x in inputs]
     rc_count = ins[0].size // n
     outs = [np.empty(rc_count, dtype=ins[0].dtype) for _ in range(n)]
@@ -144,9 +145,9 @@ def reduce_scatter(inputs: Sequence[np.ndarray], dtype: int, op: int = 0, premul
     return outs
 
 
-def reduce(inputs: Sequence[np.ndarray], dtype: int, op: int, root: int):
+def reduce(inputs: Sequence[np.ndarray], dtype: int, op: int, root: int, premul_scalar_bits: int | None = None):
     n = len(inputs)
-    d, arg = dev_op(op, dtype, n)
+    d, arg = _dev_op_or_premul(op, dtype, n, premul_scalar_bits)
     ins = [np.ascontiguousarray(x) for x in inputs]
     out = np.empty_like(ins[0])
     rc = lib().oracle_reduce(dtype, d, arg, n, root, _ptrs(ins), ins[0].size, out.ctypes.data)

@@ -120,7 +120,8 @@ def ref_proto() -> tuple[int, int]:
     return oracle.PROTO_SIMPLE, _env_int("NCCL_BUFFSIZE", 0)
 
 
-def expected(coll: str, inputs, dtype: int, op: int, root: int = 0, algo: str = ""):
+def expected(coll: str, inputs, dtype: int, op: int, root: int = 0, algo: str = "", premul: int | None = None):
+    """The oracle's result. `premul`: the storage bits of a user PreMulSum operator's scalar (`op` is then unused)."""
     if coll == "allreduce":
         # NCCL_ALGO=TREE folds every element in the chain's order; NCCL_ALGO=RING in the reference's ring order
         # over its own channel parts and loops (NCCL_MAX_CTAS / NCCL_BUFFSIZE as set for the communicator);
@@ -128,21 +129,76 @@ def expected(coll: str, inputs, dtype: int, op: int, root: int = 0, algo: str = 
         n = len(inputs)
         algo = algo or os.environ.get("NCCL_ALGO", "").upper()
         if algo == "TREE":
-            out = oracle.all_reduce_chain(inputs, dtype, op)
+            out = oracle.all_reduce_chain(inputs, dtype, op, premul)
         elif (algo == "RING" and ring_runs(n)) or ref_order_runs(n):
             proto, buff = ref_proto()
-            out = oracle.all_reduce_ring_nccl(inputs, dtype, op, ring_channels(n), buff, proto)
+            out = oracle.all_reduce_ring_nccl(inputs, dtype, op, ring_channels(n), buff, proto, premul)
         else:
-            out = oracle.all_reduce(inputs, dtype, op)
+            out = oracle.all_reduce(inputs, dtype, op, premul)
         return [out] * len(inputs)
     if coll == "reducescatter":
-        return oracle.reduce_scatter(inputs, dtype, op)
+        return oracle.reduce_scatter(inputs, dtype, op, premul)
     if coll == "allgather":
         out = oracle.all_gather(inputs)
         return [out] * len(inputs)
     if coll == "reduce":
-        return [oracle.reduce(inputs, dtype, op, root)]
+        return [oracle.reduce(inputs, dtype, op, root, premul)]
     raise ValueError(coll)
+
+
+def premul_scalars(dtype: int) -> dict[str, int]:
+    """The scalars the user PreMulSum tests run, as storage bits of `dtype`. Floats: 1, -1, 0.375 and -2.5 (exact in
+    every type), the type's rounding of 1/3 (inexact products), both zeros, the smallest subnormal, the largest
+    finite value, +Inf (e4m3 has none) and a quiet NaN. Integers: 0, 1, 3, all ones (-1), the sign bit alone,
+    0x55...."""
+    L = oracle.lib()
+    if dtype not in FLOAT_TYPES:
+        bits = 8 * np.dtype(oracle.NP_STORAGE[dtype]).itemsize
+        ones = (1 << bits) - 1
+        return {"0": 0, "1": 1, "3": 3, "ones": ones, "signbit": 1 << (bits - 1), "0x55": ones // 3}
+    vals = {"1": 1.0, "-1": -1.0, "0.375": 0.375, "-2.5": -2.5, "third": 1.0 / 3.0, "+0": 0.0, "-0": -0.0}
+    if dtype == 7:
+        enc = lambda v: int(np.float32(v).view(np.uint32))
+        rest = {"minsub": 0x00000001, "maxfinite": 0x7F7FFFFF, "inf": 0x7F800000, "nan": 0x7FC00000}
+    elif dtype == 8:
+        enc = lambda v: int(np.float64(v).view(np.uint64))
+        rest = {"minsub": 1, "maxfinite": 0x7FEFFFFFFFFFFFFF, "inf": 0x7FF0000000000000, "nan": 0x7FF8000000000000}
+    elif dtype == 6:
+        enc = lambda v: int(np.float16(v).view(np.uint16))
+        rest = {"minsub": 0x0001, "maxfinite": 0x7BFF, "inf": 0x7C00, "nan": 0x7E00}
+    elif dtype == 9:
+        enc = lambda v: int(L.oracle_f32_to_bf16(float(np.float32(v))))
+        rest = {"minsub": 0x0001, "maxfinite": 0x7F7F, "inf": 0x7F80, "nan": 0x7FC0}
+    elif dtype == 10:
+        enc = lambda v: int(L.oracle_f32_to_fp8(float(np.float32(v)), 0))
+        rest = {"minsub": 0x01, "maxfinite": 0x7E, "nan": 0x7F}
+    else:
+        enc = lambda v: int(L.oracle_f32_to_fp8(float(np.float32(v)), 1))
+        rest = {"minsub": 0x01, "maxfinite": 0x7B, "inf": 0x7C, "nan": 0x7E}
+    out = {k: enc(v) for k, v in vals.items()}
+    out.update(rest)
+    return out
+
+
+def scalar_is_finite(dtype: int, bits: int) -> bool:
+    """Whether a PreMulSum scalar (storage bits) is finite; integer scalars always are."""
+    if dtype not in FLOAT_TYPES:
+        return True
+    return bool(np.isfinite(oracle.to_f32(dtype, scalar_array(dtype, bits))[0]))
+
+
+def scalar_array(dtype: int, bits: int) -> np.ndarray:
+    """One element of dtype's storage type holding the storage bits `bits`."""
+    npdt = np.dtype(oracle.NP_STORAGE[dtype])
+    return np.array([bits], dtype=np.dtype(f"u{npdt.itemsize}")).view(npdt)
+
+
+def nan_cap_ok(want: np.ndarray, dtype: int) -> bool:
+    """The cap on the NaN-by-position rule: at least 90 % of the oracle's own result is non-NaN, hence compared bit
+    for bit (asserted for every case whose scalar is finite)."""
+    if dtype not in FLOAT_TYPES:
+        return True
+    return bool(np.isnan(oracle.to_f32(dtype, want)).mean() <= 0.10)
 
 
 def out_count(coll: str, n: int, count: int) -> int:
@@ -182,8 +238,10 @@ def case_list(n: int, quick: bool = False):
 
 
 def run_case(comms_and_streams, coll, dtype, op, count, misalign, seed, inplace=False, root=0, sync=True,
-             inputs=None, algo="", host=False):
+             inputs=None, algo="", host=False, user_ops=None, premul=None):
     """Run one collective on every (comm, stream) of this process; returns list of error strings.
+    A user PreMulSum operator: `user_ops` maps each rank to its communicator's op handle and `premul` holds the
+    scalar's storage bits for the oracle (`op` is then unused).
     `comms_and_streams` holds the ranks owned by this process: [(comm, torch stream), ...]; the
     inputs of ALL ranks are regenerated deterministically so each process can check its own ranks.
     `host` (a bool, or one per rank): that rank's buffers are pinned host memory."""
@@ -191,7 +249,7 @@ def run_case(comms_and_streams, coll, dtype, op, count, misalign, seed, inplace=
     n = comms_and_streams[0][0].nranks
     if inputs is None:
         inputs = make_inputs(n, dtype, count, seed)
-    exp = expected(coll, inputs, dtype, op, root, algo)
+    exp = expected(coll, inputs, dtype, op, root, algo, premul)
     npdt = oracle.NP_STORAGE[dtype]
     es = np.dtype(npdt).itemsize
     ocount = out_count(coll, n, count)
@@ -233,7 +291,8 @@ def run_case(comms_and_streams, coll, dtype, op, count, misalign, seed, inplace=
     torch.cuda.synchronize()
     with nccl_amd.group():
         for comm, stream, sv, rv in views:
-            launch(comm, coll, sv, rv, count, dtype, op, root, stream.cuda_stream)
+            launch(comm, coll, sv, rv, count, dtype, user_ops[comm.rank] if user_ops else op, root,
+                   stream.cuda_stream)
     errs = []
     for comm, stream, sv, rv in views:
         stream.synchronize()

@@ -51,3 +51,13 @@ static uint64_t dispatch(int dt, int op, uint64_t arg, uint64_t a, uint64_t b, i
 uint64_t nx_red(int dt, int op, uint64_t arg, uint64_t a, uint64_t b) { return dispatch(dt, op, arg, a, b, 0); }
 uint64_t nx_pre(int dt, int op, uint64_t arg, uint64_t a) { return dispatch(dt, op, arg, a, 0, 1); }
 uint64_t nx_post(int dt, int op, uint64_t arg, uint64_t a) { return dispatch(dt, op, arg, a, 0, 2); }
+// pre(x) for n elements of dtype's storage width (one call per array: the exhaustive pre-op checks)
+extern "C" void nx_pre_array(int dt, int op, uint64_t arg, const void* in, void* out, uint64_t n) {
+  const int ts = dt <= 1 || dt >= 10 ? 1 : dt == 6 || dt == 9 ? 2 : dt == 2 || dt == 3 || dt == 7 ? 4 : 8;
+  for (uint64_t i = 0; i < n; i++) {
+    uint64_t x = 0;
+    __builtin_memcpy(&x, (const char*)in + i * ts, ts);
+    const uint64_t r = dispatch(dt, op, arg, x, 0, 1);
+    __builtin_memcpy((char*)out + i * ts, &r, ts);
+  }
+}

@@ -163,3 +163,83 @@ def test_swar_byte_division_matches_functor(nx):
                 for l in range(4):
                     want = nx.nx_post(1, 4, arg, (w >> (8 * l)) & 0xff)
                     assert (got >> (8 * l)) & 0xff == want, (d, signed, hex(w), l)
+
+
+# ---- the PreMulSum pre-op (user operators: ncclRedOpCreatePreMulSum) against the oracle's one-rank PreMulSum ----
+
+def _nx_pre(nx, dtype, scalar_bits, x):
+    """nx_pre(dtype, DEV_PREMULSUM, scalar, x) for every element of x (storage array) in one call."""
+    nx.nx_pre_array.restype = None
+    nx.nx_pre_array.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                ctypes.c_uint64]
+    x = np.ascontiguousarray(x)
+    out = np.empty_like(x)
+    nx.nx_pre_array(dtype, 3, scalar_bits, x.ctypes.data, out.ctypes.data, x.size)
+    return out
+
+
+def _pre_vs_oracle(nx, dtype, x, scalars):
+    from tests import gpu_cases as G
+    for s in scalars:
+        want = oracle.all_reduce([x], dtype, premul_scalar_bits=s)
+        if G.scalar_is_finite(dtype, s):
+            assert G.nan_cap_ok(want, dtype), (dtype, hex(s))  # the NaN-by-position rule hides < 10 % of the elements
+        got = _nx_pre(nx, dtype, s, x)
+        if not G.same_bits(got, want, dtype):
+            bad = np.nonzero(G._raw(got) != G._raw(want))[0]
+            raise AssertionError(f"dtype {dtype} scalar {hex(s)}: {bad.size} candidates differ, e.g. x="
+                                 f"{[hex(int(v)) for v in G._raw(x)[bad[:4]]]} got "
+                                 f"{[hex(int(v)) for v in G._raw(got)[bad[:4]]]} want "
+                                 f"{[hex(int(v)) for v in G._raw(want)[bad[:4]]]}")
+
+
+def test_pre_array_entry_matches_scalar_entry(nx):
+    """The array entry point used below is the per-element nx_pre."""
+    x = np.arange(0, 65536, 97, dtype=np.uint16)
+    got = _nx_pre(nx, 6, 0x3555, x)
+    assert [int(v) for v in got] == [nx.nx_pre(6, 3, 0x3555, int(v)) for v in x]
+
+
+@pytest.mark.parametrize("dtype", [10, 11])
+def test_premul_pre_fp8_every_pair(nx, dtype):
+    """fp8: pre(x) = fromF(x * s) for every one of the 256 x 256 (x, scalar) pairs."""
+    _pre_vs_oracle(nx, dtype, np.arange(256, dtype=np.uint8), range(256))
+
+
+@pytest.mark.parametrize("dtype", [6, 9])
+def test_premul_pre_half_bf16_every_pattern(nx, dtype):
+    """fp16 (native _Float16 multiply) and bf16: every one of the 65,536 x patterns against the scalar list."""
+    from tests import gpu_cases as G
+    _pre_vs_oracle(nx, dtype, np.arange(65536, dtype=np.uint16), G.premul_scalars(dtype).values())
+
+
+@pytest.mark.parametrize("dtype", [7, 8])
+def test_premul_pre_fp32_fp64(nx, dtype):
+    """fp32 / fp64: random bit patterns, random moderate values and the special values against the scalar list."""
+    from tests import gpu_cases as G
+    rng = np.random.default_rng(dtype)
+    ut, ft = (np.uint32, np.float32) if dtype == 7 else (np.uint64, np.float64)
+    info = np.finfo(ft)
+    sp = np.array([np.nan, -np.nan, np.inf, -np.inf, 0.0, -0.0, info.smallest_subnormal, -info.smallest_subnormal,
+                   info.tiny, -info.tiny * (1 - info.eps), info.max, -info.max, 1.0, 3.0, -1.5], dtype=ft)
+    x = np.concatenate([rng.integers(0, np.iinfo(ut).max, 3000, dtype=ut, endpoint=True).view(ft),
+                        (rng.standard_normal(3000) * 10.0 ** rng.integers(-6, 6, 3000)).astype(ft), sp])
+    _pre_vs_oracle(nx, dtype, x, G.premul_scalars(dtype).values())
+
+
+@pytest.mark.parametrize("dtype,bits", [(0, 8), (1, 8), (2, 32), (3, 32), (4, 64), (5, 64)])
+def test_premul_pre_integers(nx, dtype, bits):
+    """Integer PreMulSum: pre(x) = (x * s) mod 2^bits, against the oracle and against Python's integers."""
+    from tests import gpu_cases as G
+    npdt = oracle.NP_STORAGE[dtype]
+    ut = np.dtype(f"u{bits // 8}")
+    ones = (1 << bits) - 1
+    rng = np.random.default_rng(bits + dtype)
+    edge = [0, 1, 2, 3, ones, ones - 1, 1 << (bits - 1), (1 << (bits - 1)) - 1, (1 << (bits - 1)) + 1, ones // 3,
+            ones // 3 * 2, 1 << (bits // 2), (1 << (bits // 2)) - 1, (1 << (bits // 2)) + 1]
+    x = np.concatenate([np.array(edge, dtype=ut), rng.integers(0, ones, 500, dtype=ut, endpoint=True)]).view(npdt)
+    for s in G.premul_scalars(dtype).values():
+        got = _nx_pre(nx, dtype, s, x)
+        want = oracle.all_reduce([x], dtype, premul_scalar_bits=s)
+        assert np.array_equal(got, want), (dtype, hex(s))
+        assert [int(v) for v in got.view(ut)] == [(int(v) * s) & ones for v in x.view(ut)], (dtype, hex(s))
