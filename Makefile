@@ -16,14 +16,14 @@ EXTRA    ?=
 COMMON   := -O3 -fPIC -std=c++17 -ffp-contract=off -fvisibility=hidden -Wall -Wno-unused-function \
             -Wno-unused-variable -Wno-unused-but-set-variable -Iinclude $(EXTRA)
 HIPFLAGS := $(COMMON) --offload-arch=$(ARCH) -fno-gpu-flush-denormals-to-zero -munsafe-fp-atomics
-HOSTSRC  := debug.cc bootstrap.cc ipc.cc transport.cc init.cc group.cc enqueue.cc register.cc tuner.cc mapcheck.cc
+HOSTSRC  := debug.cc bootstrap.cc ipc.cc transport.cc init.cc group.cc enqueue.cc p2p.cc register.cc tuner.cc mapcheck.cc
 HOSTOBJ  := $(HOSTSRC:%.cc=$(BUILD)/%.o)
 DEVSRC   := $(notdir $(wildcard $(SRCDIR)/*.hip))
 DEVOBJ   := $(DEVSRC:%.hip=$(BUILD)/%.o)
 HDRS     := $(wildcard $(SRCDIR)/*.h) include/nccl.h
 
 all: lib oracle numerics-host bootstrap-test tuner-test nccl-perf comm-examples plan-test mapcheck-test xgmi-probe atomicity-probe \
-     fp8-probe release-probe reuse-probe export-check-test barrier-probe bcast-plan-test bcast-example
+     fp8-probe release-probe reuse-probe export-check-test barrier-probe bcast-plan-test bcast-example p2p-plan-test sendrecv-example
 
 .PHONY: export-check-test
 export-check-test: tests/native/export_check_test
@@ -137,6 +137,24 @@ tests/native/bcast_example: tests/native/bcast_example.cc include/nccl.h $(LIBDI
 
 .PHONY: bcast-example
 
+# CPU test driver of the ncclSend / ncclRecv host plan (p2p.cc) and of the cut its kernel walks (device_abi.h p2pCut /
+# p2pSteps / sliceBounds, called from both sides); launches and the few HIP calls are stubbed
+p2p-plan-test: tests/native/p2p_plan_test
+
+tests/native/p2p_plan_test: tests/native/p2p_plan_test.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
+	$(CXX) -O1 -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -o $@ tests/native/p2p_plan_test.cc \
+	  $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
+
+.PHONY: p2p-plan-test
+
+# a C-ABI caller of ncclSend / ncclRecv / ncclAlltoAll written against include/nccl.h only (links with -lnccl alone)
+sendrecv-example: tests/native/sendrecv_example
+
+tests/native/sendrecv_example: tests/native/sendrecv_example.cc include/nccl.h $(LIBDIR)/libnccl.so
+	$(HIPCC) -O2 --offload-arch=$(ARCH) -Iinclude -o $@ $< -L$(LIBDIR) -lnccl -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
+
+.PHONY: sendrecv-example
+
 # Host sanitizer builds (SURVEY §5 race detection; tests/test_sanitizers.py): the bootstrap, the IPC fd server
 # and the planning code under ASan+UBSan and, separately, TSan. Host code only — no GPU code is instrumented.
 SANCXX   := $(CXX) -g -O1 -fno-omit-frame-pointer -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude
@@ -144,7 +162,7 @@ ASAN     := -fsanitize=address,undefined -fno-sanitize-recover=undefined
 TSAN     := -fsanitize=thread
 HIPRT    := -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib
 SANBIN   := build/asan/bootstrap_test build/asan/plan_test build/asan/ipc_server_test \
-            build/tsan/bootstrap_test build/tsan/ipc_server_test build/asan/bcast_plan_test
+            build/tsan/bootstrap_test build/tsan/ipc_server_test build/asan/bcast_plan_test build/asan/p2p_plan_test
 sanitize: $(SANBIN)
 
 build/asan/bootstrap_test build/tsan/bootstrap_test: tests/native/bootstrap_test.cc $(SRCDIR)/bootstrap.cc $(SRCDIR)/debug.cc $(HDRS)
@@ -165,6 +183,10 @@ tests/native/export_check_test: tests/native/export_check_test.cc $(SRCDIR)/ipc.
 build/asan/bcast_plan_test: tests/native/bcast_plan_test.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
 	@mkdir -p $(dir $@)
 	$(SANCXX) $(ASAN) -o $@ tests/native/bcast_plan_test.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
+
+build/asan/p2p_plan_test: tests/native/p2p_plan_test.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SANCXX) $(ASAN) -o $@ tests/native/p2p_plan_test.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
 
 build/asan/plan_test: tests/native/plan_test.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
 	@mkdir -p $(dir $@)

@@ -266,6 +266,40 @@ ncclResult_t ncclBcast(void* buff, size_t count, ncclDataType_t datatype, int ro
 ncclResult_t pncclBcast(void* buff, size_t count, ncclDataType_t datatype, int root, ncclComm_t comm,
                         hipStream_t stream);
 
+/* nccl.h.in:577-609 — point-to-point: rank `peer` calls the matching ncclRecv / ncclSend with the same count and
+ * datatype. Sends from a to b match b's recvs from a in issue order. Sends and recvs that must progress together to
+ * complete (an exchange, an all-to-all) are fused in one ncclGroupStart / ncclGroupEnd section; a send to oneself needs
+ * its recv in the same group. */
+ncclResult_t ncclSend(const void* sendbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,
+                      hipStream_t stream);
+ncclResult_t pncclSend(const void* sendbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,
+                       hipStream_t stream);
+ncclResult_t ncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,
+                      hipStream_t stream);
+ncclResult_t pncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,
+                       hipStream_t stream);
+
+/* nccl.h.in:533-545 — every rank sends count elements from sendbuff + j*count to rank j and receives rank i's into
+ * recvbuff + i*count. */
+ncclResult_t ncclAlltoAll(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, ncclComm_t comm,
+                          hipStream_t stream);
+ncclResult_t pncclAlltoAll(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, ncclComm_t comm,
+                           hipStream_t stream);
+
+/* nccl.h.in:547-560 — every rank sends count elements to `root`, which places rank i's at recvbuff + i*count
+ * (recvbuff is used on the root only; in place iff sendbuff == recvbuff + root*count). */
+ncclResult_t ncclGather(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, int root,
+                        ncclComm_t comm, hipStream_t stream);
+ncclResult_t pncclGather(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, int root,
+                         ncclComm_t comm, hipStream_t stream);
+
+/* nccl.h.in:562-575 — `root` sends count elements from sendbuff + i*count to rank i (sendbuff is used on the root
+ * only; in place iff recvbuff == sendbuff + root*count); every rank receives count elements into recvbuff. */
+ncclResult_t ncclScatter(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, int root,
+                         ncclComm_t comm, hipStream_t stream);
+ncclResult_t pncclScatter(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, int root,
+                          ncclComm_t comm, hipStream_t stream);
+
 /* nccl.h.in:496 — in-place iff sendbuff == recvbuff. */
 ncclResult_t ncclAllReduce(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype,
                            ncclRedOp_t op, ncclComm_t comm, hipStream_t stream);

@@ -141,7 +141,7 @@ EXPORTED = [
     "ncclReduceScatter", "ncclAllGather", "ncclGroupStart", "ncclGroupEnd",
     "ncclCommRegister", "ncclCommDeregister", "ncclCommWindowRegister", "ncclCommWindowDeregister",
     "ncclWinGetUserPtr", "ncclCommInitRankScalable", "ncclCommMemStats", "ncclGroupSimulateEnd",
-    "ncclBroadcast", "ncclBcast",
+    "ncclBroadcast", "ncclBcast", "ncclSend", "ncclRecv", "ncclAlltoAll", "ncclGather", "ncclScatter",
 ]
 
 
@@ -193,6 +193,11 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "ncclReduce": (R, [P, P, S, I, I, I, P, P]),
         "ncclBroadcast": (R, [P, P, S, I, I, P, P]),
         "ncclBcast": (R, [P, S, I, I, P, P]),
+        "ncclSend": (R, [P, S, I, I, P, P]),
+        "ncclRecv": (R, [P, S, I, I, P, P]),
+        "ncclAlltoAll": (R, [P, P, S, I, P, P]),
+        "ncclGather": (R, [P, P, S, I, I, P, P]),
+        "ncclScatter": (R, [P, P, S, I, I, P, P]),
         "ncclGroupStart": (R, []),
         "ncclGroupEnd": (R, []),
         "ncclMemAlloc": (R, [ctypes.POINTER(P), S]),
@@ -478,6 +483,46 @@ class Communicator:
         _check(load().ncclBcast(buf.data_ptr(), buf.numel(), torch_dtype_to_nccl(buf.dtype), root, self._comm,
                                 _stream_ptr(stream, self.device)), "ncclBcast")
 
+    # ---- point-to-point, and the collectives built from it ----
+    def send(self, tensor, peer: int, *, stream=None) -> None:
+        """Send `tensor` to rank `peer`, whose matching recv has the same dtype and count. Sends and recvs that must
+        progress together (an exchange) go inside one group()."""
+        self._check_tensors("send", tensor)
+        self.send_raw(tensor.data_ptr(), tensor.numel(), torch_dtype_to_nccl(tensor.dtype), peer,
+                      _stream_ptr(stream, self.device))
+
+    def recv(self, tensor, peer: int, *, stream=None) -> None:
+        """Receive into `tensor` what rank `peer` sends."""
+        self._check_tensors("recv", tensor)
+        self.recv_raw(tensor.data_ptr(), tensor.numel(), torch_dtype_to_nccl(tensor.dtype), peer,
+                      _stream_ptr(stream, self.device))
+
+    def alltoall(self, sendbuf, recvbuf, *, stream=None) -> None:
+        """Block j of sendbuf goes to rank j; block i of recvbuf comes from rank i (nranks equal blocks each)."""
+        self._check_tensors("alltoall", sendbuf, recvbuf)
+        if sendbuf.numel() != recvbuf.numel() or sendbuf.dtype != recvbuf.dtype or sendbuf.numel() % self.nranks:
+            raise ValueError("alltoall: sendbuf/recvbuf must match in dtype and hold nranks equal blocks")
+        self.alltoall_raw(sendbuf.data_ptr(), recvbuf.data_ptr(), sendbuf.numel() // self.nranks,
+                          torch_dtype_to_nccl(sendbuf.dtype), _stream_ptr(stream, self.device))
+
+    def gather(self, sendbuf, recvbuf, root: int = 0, *, stream=None) -> None:
+        """The root's recvbuf := every rank's sendbuf, rank i's at block i (recvbuf is used on the root only)."""
+        self._check_tensors("gather", sendbuf, recvbuf if self.rank == root else None)
+        if self.rank == root and (recvbuf is None or recvbuf.numel() != sendbuf.numel() * self.nranks
+                                  or recvbuf.dtype != sendbuf.dtype):
+            raise ValueError("gather: the root's recvbuf must hold nranks * sendbuf.numel() elements of the same dtype")
+        self.gather_raw(sendbuf.data_ptr(), _ptr(recvbuf) if self.rank == root else None, sendbuf.numel(),
+                        torch_dtype_to_nccl(sendbuf.dtype), root, _stream_ptr(stream, self.device))
+
+    def scatter(self, sendbuf, recvbuf, root: int = 0, *, stream=None) -> None:
+        """Every rank's recvbuf := block i of the root's sendbuf (sendbuf is used on the root only)."""
+        self._check_tensors("scatter", sendbuf if self.rank == root else None, recvbuf)
+        if self.rank == root and (sendbuf is None or sendbuf.numel() != recvbuf.numel() * self.nranks
+                                  or sendbuf.dtype != recvbuf.dtype):
+            raise ValueError("scatter: the root's sendbuf must hold nranks * recvbuf.numel() elements of the same dtype")
+        self.scatter_raw(_ptr(sendbuf) if self.rank == root else None, recvbuf.data_ptr(), recvbuf.numel(),
+                         torch_dtype_to_nccl(recvbuf.dtype), root, _stream_ptr(stream, self.device))
+
     # ---- collectives on raw device pointers (the C ABI one-to-one) ----
     def all_reduce_raw(self, send: int, recv: int, count: int, dtype: int, op: int, stream: int) -> None:
         _check(load().ncclAllReduce(send, recv, count, dtype, op, self._comm, stream), "ncclAllReduce")
@@ -494,6 +539,21 @@ class Communicator:
 
     def broadcast_raw(self, send: Optional[int], recv: int, count: int, dtype: int, root: int, stream: int) -> None:
         _check(load().ncclBroadcast(send, recv, count, dtype, root, self._comm, stream), "ncclBroadcast")
+
+    def send_raw(self, send: int, count: int, dtype: int, peer: int, stream: int) -> None:
+        _check(load().ncclSend(send, count, dtype, peer, self._comm, stream), "ncclSend")
+
+    def recv_raw(self, recv: int, count: int, dtype: int, peer: int, stream: int) -> None:
+        _check(load().ncclRecv(recv, count, dtype, peer, self._comm, stream), "ncclRecv")
+
+    def alltoall_raw(self, send: int, recv: int, count: int, dtype: int, stream: int) -> None:
+        _check(load().ncclAlltoAll(send, recv, count, dtype, self._comm, stream), "ncclAlltoAll")
+
+    def gather_raw(self, send: int, recv: Optional[int], count: int, dtype: int, root: int, stream: int) -> None:
+        _check(load().ncclGather(send, recv, count, dtype, root, self._comm, stream), "ncclGather")
+
+    def scatter_raw(self, send: Optional[int], recv: int, count: int, dtype: int, root: int, stream: int) -> None:
+        _check(load().ncclScatter(send, recv, count, dtype, root, self._comm, stream), "ncclScatter")
 
     # ---- registration (nccl.h.in:301-360; nccl4py Communicator.register_buffer / register_window) ----
     def register_buffer(self, ptr: int, size: int) -> int:

@@ -290,6 +290,9 @@ struct CommTuning {
   int64_t eagerBytes;       // NCCL_AMD_EAGER_REGISTER_BYTES: ... for collectives of at least this many bytes
   int eagerMax;             // NCCL_AMD_EAGER_REGISTER_MAX: eager registrations kept (LRU beyond it retired)
   int64_t eagerMaxBytes;    // NCCL_AMD_EAGER_REGISTER_MAX_BYTES: ... and their bytes
+  // ncclSend / ncclRecv (p2p.cc): bytes per channel part and channels per peer and direction (device_abi.h p2pCut)
+  int64_t p2pChunkBytes;    // NCCL_AMD_P2P_CHUNK_BYTES
+  int p2pMinCh, p2pMaxCh;   // NCCL_MIN_P2P_NCHANNELS / NCCL_MAX_P2P_NCHANNELS (reference src/channel.cc / init.cc)
   // size table (NCCL_AMD_SIZE_TABLE, enqueue.cc sizeTable): per rank count, the upper ends of the LL, LL128-class
   // and one-shot ranges in bytes (0 = the built-in default); loaded once at init and agreed with rank 0's
   int64_t tableLL[NCCL_AMD_MAX_RANKS + 1], tableLL128[NCCL_AMD_MAX_RANKS + 1], tableOneShot[NCCL_AMD_MAX_RANKS + 1];
@@ -554,6 +557,42 @@ ncclResult_t launchCopy(void* dst, const void* src, size_t bytes, hipStream_t st
                         int xcdShift);
 ncclResult_t warmKernels();  // load all kernel code objects on the current device (kernels.hip)
 int typeSize(ncclDataType_t t);
+
+// ---------------------------------------------------------------- point-to-point (p2p.cc)
+struct P2pOp {  // one recorded ncclSend / ncclRecv (AlltoAll / Gather / Scatter expand into these at enqueue time)
+  ncclComm* comm;
+  hipStream_t stream;
+  void* buff;
+  size_t bytes;
+  int peer;
+  bool recv;
+};
+struct P2pLaunch {  // one p2pKernel launch: the streams of rounds firstRound .. lastRound
+  int grid;
+  int firstRound, lastRound;
+  std::vector<P2pStream> streams;
+  std::vector<P2pMsg> msgs;
+};
+struct P2pSelfCopy {
+  void* dst;
+  const void* src;
+  size_t bytes;
+};
+struct P2pPlan {
+  std::vector<P2pSelfCopy> self;     // round 0: matched self sends and recvs, local copies
+  std::vector<P2pLaunch> launches;  // in launch order
+  size_t maxPeerBytes;              // the largest byte total to or from one peer (ncclGroupSimulateEnd)
+};
+// The channel cut of a message of `bytes` on this communicator (device_abi.h p2pCut with its constants)
+P2pCut p2pCutFor(const ncclComm* comm, size_t bytes);
+// The plan of one communicator's p2p ops of one group (`ops`: that communicator's, in issue order); launches nothing
+ncclResult_t p2pPlan(ncclComm* comm, const std::vector<P2pOp>& ops, P2pPlan* plan);
+// Launch a plan on `stream` (the caller forks / joins shared-GPU comms and other streams)
+ncclResult_t p2pLaunchPlan(ncclComm* comm, const P2pPlan& plan, hipStream_t stream);
+ncclResult_t launchP2pKernel(const ncclComm* comm, const P2pLaunch& l, hipStream_t stream);  // kern_gather.hip
+ncclResult_t groupDeferP2p(const P2pOp& op);
+// Pointer check (reference argcheck.cc:12-28), active with NCCL_CHECK_POINTERS=1 (enqueue.cc)
+ncclResult_t ptrCheck(const void* p, ncclComm* comm, const char* name, const char* opname);
 
 // ---------------------------------------------------------------- groups (reference src/group.cc)
 ncclResult_t groupStartInternal();

@@ -230,6 +230,67 @@ __host__ __device__ inline void llPartBounds(uint64_t part, int j, uint64_t unit
   hi = minU64(lo + part, units);
 }
 
+// ---- point-to-point (kernels.h p2pKernel, p2p.cc) ----
+// A send or a recv of `bytes` is cut the same way on both sides, from the byte count and per-communicator constants
+// alone: nch = clamp(ceil(bytes / chunk), minCh, maxCh) channel parts of alignUp(ceil(bytes / nch), 16) bytes (then
+// nch = ceil(bytes / part), so that no channel below nch is empty), part j on physical channel j, walked in slices of
+// p2pSliceBytes(slotBytes) through the pair's RS slots. An empty message has no channels: neither side handshakes.
+// Host-callable so that tests/native/p2p_plan_test walks exactly what the kernel walks.
+struct P2pCut {
+  int nch;
+  uint64_t part;
+};
+__host__ __device__ inline uint64_t p2pSliceBytes(uint64_t slotBytes) { return slotBytes & ~(uint64_t)15; }
+__host__ __device__ inline P2pCut p2pCut(uint64_t bytes, uint64_t chunk, int minCh, int maxCh) {
+  P2pCut c = {0, 0};
+  if (bytes == 0) return c;
+  if (chunk < 16) chunk = 16;
+  uint64_t nch = (bytes + chunk - 1) / chunk;
+  if (nch < (uint64_t)minCh) nch = (uint64_t)minCh;
+  if (nch > (uint64_t)maxCh) nch = (uint64_t)maxCh;
+  if (nch < 1) nch = 1;
+  c.part = ((bytes + nch - 1) / nch + 15) / 16 * 16;
+  c.nch = (int)((bytes + c.part - 1) / c.part);
+  return c;
+}
+// slices of channel part j: steps, and bytes [lo, hi) of the message at step s (sliceBounds over the whole message)
+__host__ __device__ inline int p2pSteps(uint64_t bytes, uint64_t part, uint64_t slice, int j) {
+  uint64_t lo, hi;
+  sliceBounds(part, part, j, 0, bytes, lo, hi);
+  return (int)((hi - lo + slice - 1) / slice);
+}
+
+// One message of a stream, and one stream = the in-order messages of one group to (recv == 0) or from one peer.
+// Stream i runs on workgroups wgOff .. wgOff + nch - 1 of its launch, workgroup wgOff + j on physical channel j, which
+// walks the stream's messages in order and skips those cut into j or fewer parts.
+struct P2pMsg {
+  uint64_t ptr;
+  uint64_t bytes;
+  uint64_t part;
+  uint32_t nch;
+  uint32_t pad;
+};
+struct P2pStream {
+  uint16_t wgOff, nch, msgOff, nMsgs;
+  uint8_t peer, recv;
+  uint16_t pad;
+};
+// Kernel arguments (< 4 KiB): S streams and M messages inline; a lone transfer or a pair exchange launches with the
+// small block (the host issue cost of a launch grows with its argument bytes, LLArgs above).
+constexpr int kP2pMaxStreams = 2 * (NCCL_AMD_MAX_RANKS - 1);
+constexpr int kP2pMaxMsgs = 96;
+template <int S, int M>
+struct P2pArgs {
+  const DevComm* comm;
+  int nStreams;
+  int protoFlags;    // CollArgs::protoFlags
+  int elementwise;   // NCCL_AMD_FORCE_ELEMENTWISE
+  int pad;
+  P2pStream st[S];
+  P2pMsg msg[M];
+};
+static_assert(sizeof(P2pArgs<kP2pMaxStreams, kP2pMaxMsgs>) < 4096, "kernel arguments stay under 4 KiB");
+
 // The k-th peer (k = 1 .. n-1) that channel c of rank `me` visits in a workgroup-wide multi-peer loop: the
 // staged scatter's pushes, the pull gather's reads, the zero-copy kernels' reads. Rotated by channel: with one
 // order on every channel, all of a rank's channels would sit on the SAME peer's xGMI link at step position k;

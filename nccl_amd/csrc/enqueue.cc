@@ -248,6 +248,13 @@ void loadTuning(CommTuning* t) {
   // bytes of eager-only registrations kept (their peers map them; once the owner frees one, until the next
   // collective's upkeep finds it, that HBM stays held): the least recently used beyond it are retired
   t->eagerMaxBytes = paramInt("NCCL_AMD_EAGER_REGISTER_MAX_BYTES", (int64_t)32 << 30);
+  // ncclSend / ncclRecv (p2p.cc p2pCutFor): one channel part per 128 KiB (the reference's p2p chunk), at most 32
+  // channels per peer and direction — both suppositions until a multi-GPU node is measured. The
+  // reference's NCCL_MIN_P2P_NCHANNELS / NCCL_MAX_P2P_NCHANNELS bound the count as they do there.
+  t->p2pChunkBytes = paramInt("NCCL_AMD_P2P_CHUNK_BYTES", 128 << 10);
+  if (t->p2pChunkBytes < 16) t->p2pChunkBytes = 16;
+  t->p2pMinCh = (int)std::max<int64_t>(1, paramInt("NCCL_MIN_P2P_NCHANNELS", 1));
+  t->p2pMaxCh = (int)std::max<int64_t>(1, paramInt("NCCL_MAX_P2P_NCHANNELS", 32));
   // the size table's ranges (per rank count; NCCL_AMD_SIZE_TABLE overrides rows, the three knobs below all rows)
   (void)loadSizeTable(t, paramStr("NCCL_AMD_SIZE_TABLE"));
   t->oneShotBytes = paramInt("NCCL_AMD_ONESHOT_BYTES", 0);  // 0: size table default (2 MiB / nRanks; 2 MiB at 2 ranks)
@@ -433,7 +440,7 @@ static bool isHostMemory(const void* p) {
 }
 
 // Pointer check (reference argcheck.cc:12-28), active with NCCL_CHECK_POINTERS=1.
-static ncclResult_t ptrCheck(const void* p, ncclComm* comm, const char* name, const char* opname) {
+ncclResult_t ptrCheck(const void* p, ncclComm* comm, const char* name, const char* opname) {
   hipPointerAttribute_t attr;
   hipError_t e = hipPointerGetAttributes(&attr, p);
   if (e != hipSuccess || attr.devicePointer == nullptr) {

@@ -7,8 +7,11 @@
 // concurrently at ncclGroupEnd (required when one thread creates several ranks). Kernel launches here
 // never block on peers (all connections are made at init), so one thread may drive every device of
 // the node even without a group — the group is still honoured for ordering and error reporting.
+// ncclSend / ncclRecv (p2p.cc) are recorded beside the collectives; at the group end each communicator's p2p work is
+// planned first (errors before anything launches) and launched after the group's collectives.
 #include <string.h>
 
+#include <algorithm>
 #include <functional>
 #include <map>
 #include <thread>
@@ -22,6 +25,7 @@ struct GroupState {
   int depth = 0;
   ncclResult_t error = ncclSuccess;
   std::vector<CollInfo> colls;
+  std::vector<P2pOp> p2ps;  // ncclSend / ncclRecv (p2p.cc), launched after the group's collectives
   std::vector<std::function<ncclResult_t()>> inits;
 };
 static thread_local GroupState tGroup;
@@ -35,6 +39,50 @@ ncclResult_t groupStartInternal() {
 
 ncclResult_t groupDeferColl(const CollInfo& info) {
   tGroup.colls.push_back(info);
+  return ncclSuccess;
+}
+
+ncclResult_t groupDeferP2p(const P2pOp& op) {
+  tGroup.p2ps.push_back(op);
+  return ncclSuccess;
+}
+
+// A group's p2p ops per communicator, in first-use order, each list in issue order; `stream` = the first op's, on
+// which the communicator's p2p work launches (the others are joined to it by events, p2pStreamJoin).
+struct CommP2p {
+  ncclComm* comm;
+  hipStream_t stream;
+  std::vector<P2pOp> ops;
+  P2pPlan plan;
+};
+static std::vector<CommP2p> p2pByComm(const std::vector<P2pOp>& p2ps) {
+  std::vector<CommP2p> out;
+  for (const P2pOp& op : p2ps) {
+    size_t k = 0;
+    while (k < out.size() && out[k].comm != op.comm) k++;
+    if (k == out.size()) out.push_back({op.comm, op.stream, {}, {}});
+    out[k].ops.push_back(op);
+  }
+  return out;
+}
+// `to` waits for everything enqueued on `from` so far (capture-safe: an event record and a wait)
+static ncclResult_t p2pStreamJoin(hipStream_t from, hipStream_t to) {
+  hipEvent_t ev;
+  HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  hipError_t e = hipEventRecord(ev, from);
+  if (e == hipSuccess) e = hipStreamWaitEvent(to, ev, 0);
+  (void)hipEventDestroy(ev);  // released once the record completes
+  HIPCHECK(e);
+  return ncclSuccess;
+}
+// fork (before = true): the launch stream waits for the group's other p2p streams of this comm; join: they wait for it
+static ncclResult_t p2pOtherStreams(const CommP2p& c, bool before) {
+  std::vector<hipStream_t> seen;
+  for (const P2pOp& op : c.ops) {
+    if (op.stream == c.stream || std::find(seen.begin(), seen.end(), op.stream) != seen.end()) continue;
+    seen.push_back(op.stream);
+    NCCLCHECK(before ? p2pStreamJoin(op.stream, c.stream) : p2pStreamJoin(c.stream, op.stream));
+  }
   return ncclSuccess;
 }
 
@@ -74,7 +122,7 @@ static ModelCost planCost(const PlannedColl& pc) {
 // latency per launch plus every op's transfer time, and the slowest communicator (they run concurrently on
 // their own GPUs). The reference reports the model time of the last op it planned; for a one-op group the
 // two agree.
-static ncclResult_t groupSimulate(std::vector<CollInfo>& colls, float* estimatedUs) {
+static ncclResult_t groupSimulate(std::vector<CollInfo>& colls, const std::vector<P2pOp>& p2ps, float* estimatedUs) {
   std::map<ncclComm*, double> perComm;
   std::map<ncclComm*, std::vector<PlannedColl>> open;
   auto flush = [&](ncclComm* c) {
@@ -103,6 +151,14 @@ static ncclResult_t groupSimulate(std::vector<CollInfo>& colls, float* estimated
     run.push_back(pc);
   }
   for (auto& kv : open) flush(kv.first);
+  // p2p work: planned as the group end would and dropped; one link's worth of the largest per-peer byte total (the
+  // links of different peers run side by side), priced as a two-rank direct transfer of those bytes, plus a launch
+  // latency per launch. The tuner plugin is not consulted (the reference does not consult it for p2p either).
+  for (CommP2p& c : p2pByComm(p2ps)) {
+    NCCLCHECK(p2pPlan(c.comm, c.ops, &c.plan));
+    const ModelCost m = modelCost(MODEL_DIRECT, FUNC_ALLGATHER, 2, 2 * c.plan.maxPeerBytes);
+    perComm[c.comm] += m.latUs * (double)std::max<size_t>(1, c.plan.launches.size()) + m.xferUs;
+  }
   double worst = 0;
   for (auto& kv : perComm) worst = kv.second > worst ? kv.second : worst;
   *estimatedUs = (float)worst;
@@ -125,7 +181,9 @@ ncclResult_t groupEndInternal(ncclSimInfo_t* simInfo) {
   if (--tGroup.depth > 0) return ncclSuccess;
   ncclResult_t ret = tGroup.error;
   std::vector<CollInfo> colls;
+  std::vector<P2pOp> p2pOps;
   std::vector<std::function<ncclResult_t()>> inits;
+  p2pOps.swap(tGroup.p2ps);
   colls.swap(tGroup.colls);
   inits.swap(tGroup.inits);
   tGroup.error = ncclSuccess;
@@ -148,11 +206,15 @@ ncclResult_t groupEndInternal(ncclSimInfo_t* simInfo) {
   }
   if (simInfo) {
     float us = 0;
-    NCCLCHECK(groupSimulate(colls, &us));
+    NCCLCHECK(groupSimulate(colls, p2pOps, &us));
     sim.estimatedTime = us;
     memcpy(simInfo, &sim, simSize);
     return ncclSuccess;
   }
+  // the group's p2p work is planned per communicator before anything launches: a send to self without its recv
+  // (ncclInvalidUsage) or a round that fits no launch fails the group with nothing enqueued
+  std::vector<CommP2p> p2p = p2pByComm(p2pOps);
+  for (CommP2p& c : p2p) NCCLCHECK(p2pPlan(c.comm, c.ops, &c.plan));
   int dev = 0;
   (void)hipGetDevice(&dev);
   // each communicator's upkeep first, before any of the group's kernels is launched (enqueue.cc collProgress; not
@@ -172,8 +234,26 @@ ncclResult_t groupEndInternal(ncclSimInfo_t* simInfo) {
     (void)hipSetDevice(colls[i].comm->device);
     collProgress(colls[i].comm, colls[i].stream);
   }
+  for (const CommP2p& c : p2p) {  // ... also of the communicators that only send and receive in this group
+    bool skip = false;
+    for (size_t j = 0; j < colls.size() && !skip; j++) skip = colls[j].comm == c.comm;
+    for (size_t j = 0; j < c.ops.size() && !skip; j++) {
+      hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+      skip = hipStreamIsCapturing(c.ops[j].stream, &st) != hipSuccess || st != hipStreamCaptureStatusNone;
+      (void)hipGetLastError();
+    }
+    if (skip) continue;
+    (void)hipSetDevice(c.comm->device);
+    collProgress(c.comm, c.stream);
+  }
   ncclResult_t r = ncclSuccess;
   for (size_t i = 0; i < colls.size() && r == ncclSuccess; i++) r = collFork(colls[i]);
+  for (size_t i = 0; i < p2p.size() && r == ncclSuccess; i++) {
+    (void)hipSetDevice(p2p[i].comm->device);
+    r = p2pOtherStreams(p2p[i], true);
+    const CollInfo at = {FUNC_ALLGATHER, "SendRecv", nullptr, nullptr, 0, ncclInt8, ncclSum, 0, p2p[i].comm, p2p[i].stream};
+    if (r == ncclSuccess) r = collFork(at);
+  }
   // launches in group order per comm; consecutive ops that planned onto the same kernel with the same stream,
   // type and operator become one launch (enqueue.cc batchable / launchBatch). Every rank of a comm issues the
   // same op sequence, so every rank forms the same batches.
@@ -196,7 +276,20 @@ ncclResult_t groupEndInternal(ncclSimInfo_t* simInfo) {
   }
   for (auto& kv : open)
     if (r == ncclSuccess) r = flush(kv.first);
+  // then each communicator's p2p work: after its collectives on every rank, because both kinds advance the same
+  // per-pair sequences
+  for (size_t i = 0; i < p2p.size() && r == ncclSuccess; i++) {
+    ncclComm* c = p2p[i].comm;
+    (void)hipSetDevice(c->device);
+    r = p2pLaunchPlan(c, p2p[i].plan, c->sharedDevInProcess ? c->internalStream : p2p[i].stream);
+  }
   for (size_t i = 0; i < colls.size() && r == ncclSuccess; i++) r = collJoin(colls[i]);
+  for (size_t i = 0; i < p2p.size() && r == ncclSuccess; i++) {
+    (void)hipSetDevice(p2p[i].comm->device);
+    const CollInfo at = {FUNC_ALLGATHER, "SendRecv", nullptr, nullptr, 0, ncclInt8, ncclSum, 0, p2p[i].comm, p2p[i].stream};
+    r = collJoin(at);
+    if (r == ncclSuccess) r = p2pOtherStreams(p2p[i], false);
+  }
   (void)hipSetDevice(dev);
   return r;
 }

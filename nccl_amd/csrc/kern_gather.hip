@@ -10,6 +10,10 @@ ncclResult_t launchKernGather(const LaunchPlan& p) {
     default: return launchTyped<uint64_t, 0>(p);
   }
 }
+// ncclSend / ncclRecv: bytes, in this unit beside the Broadcast kernels (p2p.cc)
+ncclResult_t launchP2pKernel(const ncclComm* comm, const P2pLaunch& l, hipStream_t stream) {
+  return launchP2pT<>(comm, l, stream);
+}
 // Force this code object to load now (see warmKernels in kernels.hip).
 hipError_t warmKernGather() {
   hipFuncAttributes attr;

@@ -18,6 +18,7 @@
 // Besides this staged kernel (collKernel, with its one-shot variant COLL_AR1) the file holds
 //   llKernel   the LL protocol for small AllReduces and group batches (flag-in-data lines, no fences),
 //   symKernel  the zero-copy kernels for buffers in symmetric windows (peers' buffers pulled directly),
+//   p2pKernel  ncclSend / ncclRecv: one workgroup per (direction, peer, channel) over the pair's RS slots and credits,
 //   oneRankKernel (PreMulSum at nRanks == 1; the nRanks == 1 copy lives in kernels.hip).
 //
 // Memory model: remote payload = `global_store_dwordx4 ... sc0 sc1` (system-scope
@@ -1257,6 +1258,84 @@ __global__ void __launch_bounds__(kThreads) kCoResident collBatchKernel(CollBatc
   storeCounters(dc, sh, c);
 }
 
+// ------------------------------------------------------------------------------------ point-to-point
+// ncclSend / ncclRecv (and the AlltoAll / Gather / Scatter built from them). One workgroup serves one
+// (direction, peer, channel): it walks that stream's messages in order, each in slices through the pair's own RS
+// slots, credits and flags on that channel — exactly the one-to-one transfer of Channel::bcastA / bcastB, so the
+// pair's sequence stays in step with every other collective. Bytes, whatever the user's datatype; always staged,
+// always pushed (NCCL_AMD_RS_PULL is not applied), no LL path (an LL epoch is a per-channel sequence every rank
+// advances). Several workgroups of one launch share a physical channel (one per direction and peer), so each
+// loads and stores ONLY its own counter word, never the channel's block (loadCounters / storeCounters).
+struct P2pShared {
+  ChanState st;  // (only `abort`: waitAll's interface)
+  uint64_t want[NCCL_AMD_MAX_RANKS];
+  uint64_t* sigPtr[1];
+  uint64_t sigVal[1];
+};
+
+template <int S, int M>
+__global__ void __launch_bounds__(kThreads) kCoResident p2pKernel(P2pArgs<S, M> a) {
+  __shared__ P2pShared sh;
+  const DevComm& dc = *a.comm;
+  const int tid = threadIdx.x, me = dc.rank, nSlots = dc.nSlots;
+  int si = 0;
+  for (int i = 1; i < a.nStreams && i < S; i++)
+    if ((int)blockIdx.x >= (int)a.st[i].wgOff) si = i;  // streams in workgroup order
+  const P2pStream sd = a.st[si];
+  const int c = (int)blockIdx.x - (int)sd.wgOff;  // part j runs on physical channel j
+  const int peer = sd.peer;
+  const bool recv = sd.recv != 0;
+  // protoFlags as in runChannel: 1 acquire on credit waits, 2 release on credit signals, 8 no release fence before
+  // data flags, 64 no acquire after data waits
+  const bool forceAcq = (a.protoFlags & 1) != 0, forceRel = (a.protoFlags & 2) != 0, noRel = (a.protoFlags & 8) != 0,
+             noAcq = (a.protoFlags & 64) != 0;
+  if (tid < NCCL_AMD_MAX_RANKS) sh.want[tid] = 0;
+  if (tid == 0) sh.st.abort = 0;
+  // malformed arguments (the host's grid check refuses them first): touch nothing
+  const bool valid = c >= 0 && c < (int)sd.nch && c < dc.maxChannels && peer < dc.nRanks && peer != me;
+  uint64_t* const ctrWord = dc.counters + ctrIndex(valid ? c : 0, recv ? CTR_RECV_RS : CTR_SEND_RS, valid ? peer : 0);
+  uint64_t seq = valid ? *ctrWord : 0;
+  __syncthreads();
+  if (!valid) return;
+  const uint64_t slice = p2pSliceBytes(dc.slotBytes);
+  const uint64_t* myFlags = dc.flags[me] + flagIndex(c, recv ? FLG_RS_READY : FLG_RS_ACK, 0);
+  uint64_t* const peerFlag = dc.flags[peer] + flagIndex(c, recv ? FLG_RS_ACK : FLG_RS_READY, me);
+  bool ok = true;
+  for (int m = 0; ok && m < (int)sd.nMsgs; m++) {
+    const P2pMsg msg = a.msg[(int)sd.msgOff + m];
+    if (c >= (int)msg.nch) continue;
+    char* const user = (char*)msg.ptr;
+    const bool aligned = (msg.ptr & 15) == 0 && !a.elementwise;  // this side's buffer only: staging is always aligned
+    const int nSteps = p2pSteps(msg.bytes, msg.part, slice, c);
+    for (int s = 0; ok && s < nSteps; s++) {
+      uint64_t lo, hi;
+      sliceBounds(msg.part, slice, c, s, msg.bytes, lo, hi);
+      const int slot = (int)(seq % (uint64_t)nSlots);
+      if (tid == 0) {
+        // send: the slot is free once the peer acked slice seq - nSlots; recv: slice seq has arrived
+        sh.want[peer] = recv ? seq + 1 : (seq + 1 > (uint64_t)nSlots ? seq + 1 - nSlots : 0);
+        sh.sigPtr[0] = peerFlag;
+        sh.sigVal[0] = seq + 1;
+      }
+      __syncthreads();
+      if (recv) {
+        ok = waitAll(dc, sh.st, myFlags, sh.want, !noAcq);
+        if (!ok) break;
+        copyRange<uint8_t, false>(user + lo, dc.staging[me] + stagingOffset(dc, c, STG_RS, slot, peer), hi - lo, aligned);
+        signalAll(sh.sigPtr, sh.sigVal, 1, forceRel);  // credit only: the slot's loads have completed
+      } else {
+        ok = waitAll(dc, sh.st, myFlags, sh.want, forceAcq);
+        if (!ok) break;
+        copyRange<uint8_t, true>(dc.staging[peer] + stagingOffset(dc, c, STG_RS, slot, me), user + lo, hi - lo, aligned);
+        signalAll(sh.sigPtr, sh.sigVal, 1, !noRel);
+      }
+      seq++;
+      __syncthreads();
+    }
+  }
+  if (tid == 0) *ctrWord = seq;
+}
+
 }  // namespace ncclamd
 #include "pipe.h"  // ring and chain (NCCL_ALGO=RING / TREE) on the same staging and credits
 namespace ncclamd {
@@ -2161,6 +2240,29 @@ inline ncclResult_t launchBcast(const LaunchPlan& p) {
   if (p.algo == ALGO_LL) launchLL<T, 0>(p);
   else if (p.algo == ALGO_DIRECT) launchColl<T, 0, COLL_BCAST>(p);
   else return ncclInternalError;
+  HIPCHECK(hipGetLastError());
+  return ncclSuccess;
+}
+
+// One p2pKernel launch with the smallest argument block that holds it (a template only so that the one unit that
+// calls it, kern_gather.hip, instantiates the kernels)
+template <int S, int M>
+inline void launchP2pArgs(const ncclComm* comm, const P2pLaunch& l, hipStream_t stream) {
+  P2pArgs<S, M> a;
+  __builtin_memset(&a, 0, sizeof(a));
+  a.comm = comm->devComm;
+  a.nStreams = (int)l.streams.size();
+  a.protoFlags = comm->tune.protoFlags;
+  a.elementwise = comm->tune.forceElementwise;
+  for (size_t i = 0; i < l.streams.size(); i++) a.st[i] = l.streams[i];
+  for (size_t i = 0; i < l.msgs.size(); i++) a.msg[i] = l.msgs[i];
+  NCCL_AMD_LAUNCH((p2pKernel<S, M>), dim3(l.grid), dim3(kThreads), 0, stream, a);
+}
+template <int SMALL = 2>
+inline ncclResult_t launchP2pT(const ncclComm* comm, const P2pLaunch& l, hipStream_t stream) {
+  if (l.streams.size() > (size_t)kP2pMaxStreams || l.msgs.size() > (size_t)kP2pMaxMsgs || l.grid < 1) return ncclInternalError;
+  if (l.streams.size() <= (size_t)SMALL && l.msgs.size() <= (size_t)SMALL) launchP2pArgs<SMALL, SMALL>(comm, l, stream);
+  else launchP2pArgs<kP2pMaxStreams, kP2pMaxMsgs>(comm, l, stream);
   HIPCHECK(hipGetLastError());
   return ncclSuccess;
 }
