@@ -16,14 +16,15 @@ EXTRA    ?=
 COMMON   := -O3 -fPIC -std=c++17 -ffp-contract=off -fvisibility=hidden -Wall -Wno-unused-function \
             -Wno-unused-variable -Wno-unused-but-set-variable -Iinclude $(EXTRA)
 HIPFLAGS := $(COMMON) --offload-arch=$(ARCH) -fno-gpu-flush-denormals-to-zero -munsafe-fp-atomics
-HOSTSRC  := debug.cc bootstrap.cc ipc.cc transport.cc init.cc group.cc enqueue.cc p2p.cc register.cc tuner.cc mapcheck.cc
+HOSTSRC  := debug.cc bootstrap.cc ipc.cc transport.cc init.cc group.cc enqueue.cc p2p.cc rma.cc register.cc tuner.cc mapcheck.cc
 HOSTOBJ  := $(HOSTSRC:%.cc=$(BUILD)/%.o)
 DEVSRC   := $(notdir $(wildcard $(SRCDIR)/*.hip))
 DEVOBJ   := $(DEVSRC:%.hip=$(BUILD)/%.o)
 HDRS     := $(wildcard $(SRCDIR)/*.h) include/nccl.h
 
 all: lib oracle numerics-host bootstrap-test tuner-test nccl-perf comm-examples plan-test mapcheck-test xgmi-probe atomicity-probe \
-     fp8-probe release-probe reuse-probe export-check-test barrier-probe bcast-plan-test bcast-example p2p-plan-test sendrecv-example
+     fp8-probe release-probe reuse-probe export-check-test barrier-probe bcast-plan-test bcast-example p2p-plan-test sendrecv-example \
+     rma-plan-test
 
 .PHONY: export-check-test
 export-check-test: tests/native/export_check_test
@@ -147,6 +148,16 @@ tests/native/p2p_plan_test: tests/native/p2p_plan_test.cc $(SRCDIR)/p2p.cc $(SRC
 
 .PHONY: p2p-plan-test
 
+# CPU test driver of the ncclPutSignal / ncclSignal / ncclWaitSignal host plan and argument checks (rma.cc, group.cc);
+# launches and the few HIP calls are stubbed
+rma-plan-test: tests/native/rma_plan_test
+
+tests/native/rma_plan_test: tests/native/rma_plan_test.cc $(SRCDIR)/rma.cc $(SRCDIR)/group.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
+	$(CXX) -O1 -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -o $@ tests/native/rma_plan_test.cc \
+	  $(SRCDIR)/rma.cc $(SRCDIR)/group.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
+
+.PHONY: rma-plan-test
+
 # a C-ABI caller of ncclSend / ncclRecv / ncclAlltoAll written against include/nccl.h only (links with -lnccl alone)
 sendrecv-example: tests/native/sendrecv_example
 
@@ -162,7 +173,8 @@ ASAN     := -fsanitize=address,undefined -fno-sanitize-recover=undefined
 TSAN     := -fsanitize=thread
 HIPRT    := -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib
 SANBIN   := build/asan/bootstrap_test build/asan/plan_test build/asan/ipc_server_test \
-            build/tsan/bootstrap_test build/tsan/ipc_server_test build/asan/bcast_plan_test build/asan/p2p_plan_test
+            build/tsan/bootstrap_test build/tsan/ipc_server_test build/asan/bcast_plan_test build/asan/p2p_plan_test \
+            build/asan/rma_plan_test
 sanitize: $(SANBIN)
 
 build/asan/bootstrap_test build/tsan/bootstrap_test: tests/native/bootstrap_test.cc $(SRCDIR)/bootstrap.cc $(SRCDIR)/debug.cc $(HDRS)
@@ -187,6 +199,10 @@ build/asan/bcast_plan_test: tests/native/bcast_plan_test.cc $(SRCDIR)/enqueue.cc
 build/asan/p2p_plan_test: tests/native/p2p_plan_test.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
 	@mkdir -p $(dir $@)
 	$(SANCXX) $(ASAN) -o $@ tests/native/p2p_plan_test.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
+
+build/asan/rma_plan_test: tests/native/rma_plan_test.cc $(SRCDIR)/rma.cc $(SRCDIR)/group.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SANCXX) $(ASAN) -o $@ tests/native/rma_plan_test.cc $(SRCDIR)/rma.cc $(SRCDIR)/group.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
 
 build/asan/plan_test: tests/native/plan_test.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
 	@mkdir -p $(dir $@)

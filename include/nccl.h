@@ -279,6 +279,33 @@ ncclResult_t ncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, int
 ncclResult_t pncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm,
                        hipStream_t stream);
 
+/* nccl.h.in:612-692 — one-sided operations on registered windows. ncclPutSignal writes count elements from localbuff
+ * (inside a NCCL_WIN_COLL_SYMMETRIC window of this communicator) into rank `peer`'s part of peerWin — the caller's own
+ * handle from the collective registration — at byte offset peerWinOffset, then raises by one the signal `peer` holds
+ * for this rank; ncclSignal raises it without data. A raised signal means that put's data is delivered and every
+ * earlier put or signal of this rank to that peer has signalled; puts of one rank to one peer deliver their data in
+ * issue order (of two puts to overlapping bytes the later one's data stays). ncclWaitSignal waits, on the stream, until
+ * descs[i].opCnt further signals from descs[i].peer have arrived and consumes them (descriptors naming one peer add
+ * up); what the stream runs next sees the data of those puts. sigIdx, ctx and flags must be 0. Pure enqueues: legal in
+ * a group and under stream capture, never waiting for the peer on the host; peer == own rank is legal. Operations of
+ * one communicator must be ordered by the caller's streams, as collectives are. */
+ncclResult_t ncclPutSignal(const void* localbuff, size_t count, ncclDataType_t datatype, int peer, ncclWindow_t peerWin,
+                           size_t peerWinOffset, int sigIdx, int ctx, unsigned int flags, ncclComm_t comm,
+                           hipStream_t stream);
+ncclResult_t pncclPutSignal(const void* localbuff, size_t count, ncclDataType_t datatype, int peer, ncclWindow_t peerWin,
+                            size_t peerWinOffset, int sigIdx, int ctx, unsigned int flags, ncclComm_t comm,
+                            hipStream_t stream);
+ncclResult_t ncclSignal(int peer, int sigIdx, int ctx, unsigned int flags, ncclComm_t comm, hipStream_t stream);
+ncclResult_t pncclSignal(int peer, int sigIdx, int ctx, unsigned int flags, ncclComm_t comm, hipStream_t stream);
+typedef struct {
+  int opCnt;  /* number of signal operations to wait for */
+  int peer;   /* the rank whose signals are awaited */
+  int sigIdx; /* signal index (0) */
+  int ctx;    /* context (0) */
+} ncclWaitSignalDesc_t;
+ncclResult_t ncclWaitSignal(int nDesc, ncclWaitSignalDesc_t* signalDescs, ncclComm_t comm, hipStream_t stream);
+ncclResult_t pncclWaitSignal(int nDesc, ncclWaitSignalDesc_t* signalDescs, ncclComm_t comm, hipStream_t stream);
+
 /* nccl.h.in:533-545 — every rank sends count elements from sendbuff + j*count to rank j and receives rank i's into
  * recvbuff + i*count. */
 ncclResult_t ncclAlltoAll(const void* sendbuff, void* recvbuff, size_t count, ncclDataType_t datatype, ncclComm_t comm,

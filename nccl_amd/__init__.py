@@ -95,6 +95,10 @@ class GroupSimInfo:
     estimated_time: float  # seconds
 
 
+class WaitSignalDesc(ctypes.Structure):  # ncclWaitSignalDesc_t, nccl.h.in:668-673
+    _fields_ = [("opCnt", ctypes.c_int), ("peer", ctypes.c_int), ("sigIdx", ctypes.c_int), ("ctx", ctypes.c_int)]
+
+
 class MemStat(enum.IntEnum):  # ncclCommMemStat_t, nccl.h.in:333-338
     GPU_MEM_SUSPEND = 0
     GPU_MEM_SUSPENDED = 1
@@ -142,6 +146,7 @@ EXPORTED = [
     "ncclCommRegister", "ncclCommDeregister", "ncclCommWindowRegister", "ncclCommWindowDeregister",
     "ncclWinGetUserPtr", "ncclCommInitRankScalable", "ncclCommMemStats", "ncclGroupSimulateEnd",
     "ncclBroadcast", "ncclBcast", "ncclSend", "ncclRecv", "ncclAlltoAll", "ncclGather", "ncclScatter",
+    "ncclPutSignal", "ncclSignal", "ncclWaitSignal",
 ]
 
 
@@ -198,6 +203,9 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "ncclAlltoAll": (R, [P, P, S, I, P, P]),
         "ncclGather": (R, [P, P, S, I, I, P, P]),
         "ncclScatter": (R, [P, P, S, I, I, P, P]),
+        "ncclPutSignal": (R, [P, S, I, I, P, S, I, I, ctypes.c_uint, P, P]),
+        "ncclSignal": (R, [I, I, I, ctypes.c_uint, P, P]),
+        "ncclWaitSignal": (R, [I, ctypes.POINTER(WaitSignalDesc), P, P]),
         "ncclGroupStart": (R, []),
         "ncclGroupEnd": (R, []),
         "ncclMemAlloc": (R, [ctypes.POINTER(P), S]),
@@ -523,6 +531,25 @@ class Communicator:
         self.scatter_raw(_ptr(sendbuf) if self.rank == root else None, recvbuf.data_ptr(), recvbuf.numel(),
                          torch_dtype_to_nccl(recvbuf.dtype), root, _stream_ptr(stream, self.device))
 
+    # ---- one-sided operations on registered windows ----
+    def put_signal(self, tensor, peer: int, win, offset: int = 0, *, stream=None) -> None:
+        """Write `tensor` (inside a WIN_COLL_SYMMETRIC window of this communicator) into rank `peer`'s part of window
+        `win` at byte `offset`, then raise the signal `peer` holds for this rank by one."""
+        self._check_tensors("put_signal", tensor)
+        self.put_signal_raw(tensor.data_ptr(), tensor.numel(), torch_dtype_to_nccl(tensor.dtype), peer, win, offset,
+                            _stream_ptr(stream, self.device))
+
+    def signal(self, peer: int, *, stream=None, sig_idx: int = 0, ctx: int = 0, flags: int = 0) -> None:
+        """Raise the signal rank `peer` holds for this rank by one; no data moves (ncclSignal)."""
+        _check(load().ncclSignal(peer, sig_idx, ctx, flags, self._comm, _stream_ptr(stream, self.device)), "ncclSignal")
+
+    def wait_signal(self, descs, *, stream=None) -> None:
+        """ncclWaitSignal: `descs` is a sequence of (peer, op_cnt) pairs or WaitSignalDesc; the stream waits until
+        op_cnt further signals from each peer have arrived and consumes them (entries naming one peer add up)."""
+        ds = [d if isinstance(d, WaitSignalDesc) else WaitSignalDesc(int(d[1]), int(d[0]), 0, 0) for d in descs]
+        arr = (WaitSignalDesc * max(1, len(ds)))(*ds)
+        _check(load().ncclWaitSignal(len(ds), arr, self._comm, _stream_ptr(stream, self.device)), "ncclWaitSignal")
+
     # ---- collectives on raw device pointers (the C ABI one-to-one) ----
     def all_reduce_raw(self, send: int, recv: int, count: int, dtype: int, op: int, stream: int) -> None:
         _check(load().ncclAllReduce(send, recv, count, dtype, op, self._comm, stream), "ncclAllReduce")
@@ -554,6 +581,12 @@ class Communicator:
 
     def scatter_raw(self, send: Optional[int], recv: int, count: int, dtype: int, root: int, stream: int) -> None:
         _check(load().ncclScatter(send, recv, count, dtype, root, self._comm, stream), "ncclScatter")
+
+    def put_signal_raw(self, local: Optional[int], count: int, dtype: int, peer: int, win, offset: int, stream: int,
+                       sig_idx: int = 0, ctx: int = 0, flags: int = 0) -> None:
+        h = win.handle if isinstance(win, Window) else win
+        _check(load().ncclPutSignal(local, count, dtype, peer, h, offset, sig_idx, ctx, flags, self._comm, stream),
+               "ncclPutSignal")
 
     # ---- registration (nccl.h.in:301-360; nccl4py Communicator.register_buffer / register_window) ----
     def register_buffer(self, ptr: int, size: int) -> int:

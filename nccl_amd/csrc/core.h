@@ -315,6 +315,7 @@ struct ncclWindow_vidmem {
   size_t size;
   int flags;
   char* peerPtr[NCCL_AMD_MAX_RANKS];  // every rank's window base as mapped in this process
+  size_t peerSize[NCCL_AMD_MAX_RANKS];  // the bytes each rank registered (ncclPutSignal's bound; equal when symmetric)
   uint64_t peerBase[NCCL_AMD_MAX_RANKS];  // allocation bases of IPC-mapped peers (0: direct pointer)
 };
 
@@ -593,6 +594,42 @@ ncclResult_t launchP2pKernel(const ncclComm* comm, const P2pLaunch& l, hipStream
 ncclResult_t groupDeferP2p(const P2pOp& op);
 // Pointer check (reference argcheck.cc:12-28), active with NCCL_CHECK_POINTERS=1 (enqueue.cc)
 ncclResult_t ptrCheck(const void* p, ncclComm* comm, const char* name, const char* opname);
+
+// ---------------------------------------------------------------- one-sided operations (rma.cc)
+struct RmaOp {  // one recorded ncclPutSignal / ncclSignal (wait == false) or ncclWaitSignal (wait == true)
+  ncclComm* comm;
+  hipStream_t stream;
+  bool wait;
+  const void* src;  // put: localbuff
+  char* dst;        // put: the target in the peer's window as mapped here
+  size_t bytes;     // put: 0 = a signal
+  int peer;
+  uint32_t waitCnt[NCCL_AMD_MAX_RANKS];  // wait: signals to consume per peer (descriptors of one peer added up)
+};
+struct RmaLaunch {  // one rmaPutKernel launch: whole streams of one batch
+  int grid;
+  std::vector<RmaStream> streams;
+  std::vector<RmaMsg> msgs;
+};
+struct RmaStep {  // in launch order: a put launch, or a wait
+  bool wait;
+  hipStream_t stream;
+  RmaLaunch put;
+  RmaWaitArgs w;
+};
+struct RmaPlan {
+  std::vector<RmaStep> steps;
+  size_t maxPeerBytes;  // the largest byte total put to one peer (ncclGroupSimulateEnd)
+};
+// The plan of one communicator's one-sided ops of one group (`ops`: that communicator's, in issue order): a batch is a
+// run of consecutive puts and signals on one stream; a wait, another stream or a 97th message to one peer closes it.
+// A batch's streams (one per peer) are packed whole into launches of at most chanCap workgroups. Launches nothing.
+ncclResult_t rmaPlan(ncclComm* comm, const std::vector<RmaOp>& ops, RmaPlan* plan);
+// Launch a plan; each step on its own stream, or on the communicator's internal stream (the caller forks / joins)
+ncclResult_t rmaLaunchPlan(ncclComm* comm, const RmaPlan& plan);
+ncclResult_t launchRmaPutKernel(const ncclComm* comm, const RmaLaunch& l, hipStream_t stream);   // kern_gather.hip
+ncclResult_t launchRmaWaitKernel(const ncclComm* comm, const RmaWaitArgs& w, hipStream_t stream);  // kern_gather.hip
+ncclResult_t groupDeferRma(const RmaOp& op);
 
 // ---------------------------------------------------------------- groups (reference src/group.cc)
 ncclResult_t groupStartInternal();

@@ -15,6 +15,8 @@
 //                          which `from` entered / published its reduced block / finished reading peers
 //       REG_SEND / REG_RECV[c][from] = `from`'s registered send / recv buffer as mapped in MY address space,
 //                          stored before its SYM_ENTER (zero-copy collectives on ncclCommRegister buffers)
+//       SIGNAL[0][from]    = number of signals `from` has raised for me (ncclPutSignal / ncclSignal; monotonic,
+//                          channel 0's row only)
 //     A word is written by exactly one remote rank and polled only by its owner.
 //
 //   LL lines (same uncached allocation as the flags, at DevComm::llOffset; reference prims_ll.h:108-158)
@@ -29,7 +31,7 @@
 //     A separate area, so stale LL64 payload can never alias an LL flag position and vice versa.
 //
 //   counters (plain device memory, local)
-//     uint64 [channel][ctr kind < 5 (sendRS, recvRS, sendAG, recvAG, sym)][peer < NCCL_AMD_MAX_RANKS]
+//     uint64 [channel][ctr kind < CTR_KINDS (sendRS, recvRS, sendAG, recvAG, sym, ...)][peer < NCCL_AMD_MAX_RANKS]
 //     Per-connection step counters (reference: conn->step, src/device/prims_simple.h:100-173),
 //     kept in device memory so a captured hipGraph replays correctly.
 #pragma once
@@ -47,14 +49,19 @@ enum StagingKind { STG_RS = 0, STG_AG = 1, STG_KINDS = 2 };
 // FLG_REG_SEND / FLG_REG_RECV: the device-side pointer exchange of registered (ncclCommRegister) buffers —
 // before its ENTER signal, rank `from` stores its send / recv buffer AS MAPPED IN THIS PROCESS into these
 // words of the same channel (reference: the ptrExchange slots of prims_simple.h:748-846).
+// FLG_SIGNAL and CTR_SIG_SENT / CTR_SIG_SEEN / CTR_SIG_ARRIVE: the one-sided operations (kernels.h rmaPutKernel /
+// rmaWaitKernel), channel 0's rows only: the signal word per sender; signals this rank raised per
+// peer, signals it consumed per peer, and the workgroups of a put launch that finished a message for a peer. Only the
+// one-sided kernels touch these rows: the channel kernels load and store rows below CTR_CHAN_KINDS.
 enum FlagKind {
   FLG_RS_READY = 0, FLG_RS_ACK = 1, FLG_AG_READY = 2, FLG_AG_ACK = 3,
   FLG_SYM_ENTER = 4, FLG_SYM_MID = 5, FLG_SYM_DONE = 6, FLG_PULL_READY = 7, FLG_PULL_ACK = 8,
-  FLG_REG_SEND = 9, FLG_REG_RECV = 10, FLG_KINDS = 11
+  FLG_REG_SEND = 9, FLG_REG_RECV = 10, FLG_SIGNAL = 11, FLG_KINDS = 12
 };
 enum CtrKind {
   CTR_SEND_RS = 0, CTR_RECV_RS = 1, CTR_SEND_AG = 2, CTR_RECV_AG = 3, CTR_SYM = 4, CTR_LL = 5,
-  CTR_PULL_PUB = 6, CTR_PULL_GOT = 7, CTR_KINDS = 8
+  CTR_PULL_PUB = 6, CTR_PULL_GOT = 7, CTR_CHAN_KINDS = 8,  // the rows a channel kernel keeps in LDS (ChanState)
+  CTR_SIG_SENT = 8, CTR_SIG_SEEN = 9, CTR_SIG_ARRIVE = 10, CTR_KINDS = 11
 };
 
 // Ring / chain kernels (pipe.h; NCCL_ALGO=RING / TREE)
@@ -290,6 +297,47 @@ struct P2pArgs {
   P2pMsg msg[M];
 };
 static_assert(sizeof(P2pArgs<kP2pMaxStreams, kP2pMaxMsgs>) < 4096, "kernel arguments stay under 4 KiB");
+
+// ---- one-sided operations (kernels.h rmaPutKernel / rmaWaitKernel, rma.cc) ----
+// One put or signal (bytes == 0: a signal, no workgroup copies) and one stream = the in-order messages of one batch to
+// one peer. Stream i runs on workgroups wgOff .. wgOff + nch - 1 of its launch; workgroup wgOff + j copies part j
+// (p2pCut's) of every message cut into more than j parts, and workgroup wgOff posts the stream's signals in order.
+struct RmaMsg {
+  uint64_t src;    // localbuff
+  uint64_t dst;    // the target inside the peer's window, as mapped in this process
+  uint64_t bytes;
+  uint64_t part;
+  uint32_t nch;
+  uint32_t pad;
+};
+struct RmaStream {
+  uint16_t wgOff, nch, msgOff, nMsgs;
+  uint8_t peer;
+  uint8_t pad[3];
+};
+constexpr int kRmaMaxStreams = NCCL_AMD_MAX_RANKS;  // one per peer, self included
+constexpr int kRmaMaxMsgs = 96;
+template <int S, int M>
+struct RmaArgs {
+  const DevComm* comm;
+  int nStreams;
+  int protoFlags;    // CollArgs::protoFlags (8: no release fence before a signal)
+  int elementwise;   // NCCL_AMD_FORCE_ELEMENTWISE
+  int pad;
+  RmaStream st[S];
+  RmaMsg msg[M];
+};
+static_assert(sizeof(RmaArgs<kRmaMaxStreams, kRmaMaxMsgs>) < 4096, "kernel arguments stay under 4 KiB");
+// ncclWaitSignal: per peer, the signals to consume (descriptors naming one peer added up); lane i serves entry i
+struct RmaWaitArgs {
+  const DevComm* comm;
+  int n;
+  int pad;
+  struct {
+    int peer;
+    uint32_t opCnt;
+  } d[NCCL_AMD_MAX_RANKS];
+};
 
 // The k-th peer (k = 1 .. n-1) that channel c of rank `me` visits in a workgroup-wide multi-peer loop: the
 // staged scatter's pushes, the pull gather's reads, the zero-copy kernels' reads. Rotated by channel: with one

@@ -9,6 +9,8 @@
 // the node even without a group — the group is still honoured for ordering and error reporting.
 // ncclSend / ncclRecv (p2p.cc) are recorded beside the collectives; at the group end each communicator's p2p work is
 // planned first (errors before anything launches) and launched after the group's collectives.
+// The one-sided operations (rma.cc) likewise: planned first, launched per communicator in issue order after that
+// communicator's collectives and p2p launches.
 #include <string.h>
 
 #include <algorithm>
@@ -26,6 +28,7 @@ struct GroupState {
   ncclResult_t error = ncclSuccess;
   std::vector<CollInfo> colls;
   std::vector<P2pOp> p2ps;  // ncclSend / ncclRecv (p2p.cc), launched after the group's collectives
+  std::vector<RmaOp> rmas;  // ncclPutSignal / ncclSignal / ncclWaitSignal (rma.cc), launched after those
   std::vector<std::function<ncclResult_t()>> inits;
 };
 static thread_local GroupState tGroup;
@@ -45,6 +48,34 @@ ncclResult_t groupDeferColl(const CollInfo& info) {
 ncclResult_t groupDeferP2p(const P2pOp& op) {
   tGroup.p2ps.push_back(op);
   return ncclSuccess;
+}
+
+ncclResult_t groupDeferRma(const RmaOp& op) {
+  tGroup.rmas.push_back(op);
+  return ncclSuccess;
+}
+
+// A group's one-sided ops per communicator, in first-use order, each list in issue order
+struct CommRma {
+  ncclComm* comm;
+  std::vector<RmaOp> ops;
+  RmaPlan plan;
+  std::vector<hipStream_t> streams;  // the distinct streams its ops name (a shared-GPU comm forks from / joins to each)
+};
+static std::vector<CommRma> rmaByComm(const std::vector<RmaOp>& rmas) {
+  std::vector<CommRma> out;
+  for (const RmaOp& op : rmas) {
+    size_t k = 0;
+    while (k < out.size() && out[k].comm != op.comm) k++;
+    if (k == out.size()) out.push_back({op.comm, {}, {}, {}});
+    out[k].ops.push_back(op);
+    if (std::find(out[k].streams.begin(), out[k].streams.end(), op.stream) == out[k].streams.end())
+      out[k].streams.push_back(op.stream);
+  }
+  return out;
+}
+static CollInfo rmaAt(const CommRma& c, hipStream_t stream) {
+  return {FUNC_ALLGATHER, "PutSignal", nullptr, nullptr, 0, ncclInt8, ncclSum, 0, c.comm, stream};
 }
 
 // A group's p2p ops per communicator, in first-use order, each list in issue order; `stream` = the first op's, on
@@ -122,7 +153,8 @@ static ModelCost planCost(const PlannedColl& pc) {
 // latency per launch plus every op's transfer time, and the slowest communicator (they run concurrently on
 // their own GPUs). The reference reports the model time of the last op it planned; for a one-op group the
 // two agree.
-static ncclResult_t groupSimulate(std::vector<CollInfo>& colls, const std::vector<P2pOp>& p2ps, float* estimatedUs) {
+static ncclResult_t groupSimulate(std::vector<CollInfo>& colls, const std::vector<P2pOp>& p2ps,
+                                  const std::vector<RmaOp>& rmas, float* estimatedUs) {
   std::map<ncclComm*, double> perComm;
   std::map<ncclComm*, std::vector<PlannedColl>> open;
   auto flush = [&](ncclComm* c) {
@@ -159,6 +191,13 @@ static ncclResult_t groupSimulate(std::vector<CollInfo>& colls, const std::vecto
     const ModelCost m = modelCost(MODEL_DIRECT, FUNC_ALLGATHER, 2, 2 * c.plan.maxPeerBytes);
     perComm[c.comm] += m.latUs * (double)std::max<size_t>(1, c.plan.launches.size()) + m.xferUs;
   }
+  // one-sided work: planned and dropped the same way, priced with the p2p model (one link's worth of the largest
+  // per-peer byte total, a launch latency per launch, waits included); no tuner, no NCCL_ALGO / NCCL_PROTO
+  for (CommRma& c : rmaByComm(rmas)) {
+    NCCLCHECK(rmaPlan(c.comm, c.ops, &c.plan));
+    const ModelCost m = modelCost(MODEL_DIRECT, FUNC_ALLGATHER, 2, 2 * c.plan.maxPeerBytes);
+    perComm[c.comm] += m.latUs * (double)std::max<size_t>(1, c.plan.steps.size()) + m.xferUs;
+  }
   double worst = 0;
   for (auto& kv : perComm) worst = kv.second > worst ? kv.second : worst;
   *estimatedUs = (float)worst;
@@ -182,8 +221,10 @@ ncclResult_t groupEndInternal(ncclSimInfo_t* simInfo) {
   ncclResult_t ret = tGroup.error;
   std::vector<CollInfo> colls;
   std::vector<P2pOp> p2pOps;
+  std::vector<RmaOp> rmaOps;
   std::vector<std::function<ncclResult_t()>> inits;
   p2pOps.swap(tGroup.p2ps);
+  rmaOps.swap(tGroup.rmas);
   colls.swap(tGroup.colls);
   inits.swap(tGroup.inits);
   tGroup.error = ncclSuccess;
@@ -206,7 +247,7 @@ ncclResult_t groupEndInternal(ncclSimInfo_t* simInfo) {
   }
   if (simInfo) {
     float us = 0;
-    NCCLCHECK(groupSimulate(colls, p2pOps, &us));
+    NCCLCHECK(groupSimulate(colls, p2pOps, rmaOps, &us));
     sim.estimatedTime = us;
     memcpy(simInfo, &sim, simSize);
     return ncclSuccess;
@@ -215,6 +256,8 @@ ncclResult_t groupEndInternal(ncclSimInfo_t* simInfo) {
   // (ncclInvalidUsage) or a round that fits no launch fails the group with nothing enqueued
   std::vector<CommP2p> p2p = p2pByComm(p2pOps);
   for (CommP2p& c : p2p) NCCLCHECK(p2pPlan(c.comm, c.ops, &c.plan));
+  std::vector<CommRma> rma = rmaByComm(rmaOps);  // ... and the one-sided work: every planning failure surfaces here
+  for (CommRma& c : rma) NCCLCHECK(rmaPlan(c.comm, c.ops, &c.plan));
   int dev = 0;
   (void)hipGetDevice(&dev);
   // each communicator's upkeep first, before any of the group's kernels is launched (enqueue.cc collProgress; not
@@ -246,6 +289,19 @@ ncclResult_t groupEndInternal(ncclSimInfo_t* simInfo) {
     (void)hipSetDevice(c.comm->device);
     collProgress(c.comm, c.stream);
   }
+  for (const CommRma& c : rma) {  // ... or only put, signal and wait
+    bool skip = false;
+    for (size_t j = 0; j < colls.size() && !skip; j++) skip = colls[j].comm == c.comm;
+    for (size_t j = 0; j < p2p.size() && !skip; j++) skip = p2p[j].comm == c.comm;
+    for (size_t j = 0; j < c.streams.size() && !skip; j++) {
+      hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+      skip = hipStreamIsCapturing(c.streams[j], &st) != hipSuccess || st != hipStreamCaptureStatusNone;
+      (void)hipGetLastError();
+    }
+    if (skip) continue;
+    (void)hipSetDevice(c.comm->device);
+    collProgress(c.comm, c.streams[0]);
+  }
   ncclResult_t r = ncclSuccess;
   for (size_t i = 0; i < colls.size() && r == ncclSuccess; i++) r = collFork(colls[i]);
   for (size_t i = 0; i < p2p.size() && r == ncclSuccess; i++) {
@@ -254,6 +310,8 @@ ncclResult_t groupEndInternal(ncclSimInfo_t* simInfo) {
     const CollInfo at = {FUNC_ALLGATHER, "SendRecv", nullptr, nullptr, 0, ncclInt8, ncclSum, 0, p2p[i].comm, p2p[i].stream};
     if (r == ncclSuccess) r = collFork(at);
   }
+  for (size_t i = 0; i < rma.size() && r == ncclSuccess; i++)
+    for (size_t j = 0; j < rma[i].streams.size() && r == ncclSuccess; j++) r = collFork(rmaAt(rma[i], rma[i].streams[j]));
   // launches in group order per comm; consecutive ops that planned onto the same kernel with the same stream,
   // type and operator become one launch (enqueue.cc batchable / launchBatch). Every rank of a comm issues the
   // same op sequence, so every rank forms the same batches.
@@ -283,6 +341,11 @@ ncclResult_t groupEndInternal(ncclSimInfo_t* simInfo) {
     (void)hipSetDevice(c->device);
     r = p2pLaunchPlan(c, p2p[i].plan, c->sharedDevInProcess ? c->internalStream : p2p[i].stream);
   }
+  // then its one-sided work, in issue order: its signals follow everything the communicator does in this group
+  for (size_t i = 0; i < rma.size() && r == ncclSuccess; i++) {
+    (void)hipSetDevice(rma[i].comm->device);
+    r = rmaLaunchPlan(rma[i].comm, rma[i].plan);
+  }
   for (size_t i = 0; i < colls.size() && r == ncclSuccess; i++) r = collJoin(colls[i]);
   for (size_t i = 0; i < p2p.size() && r == ncclSuccess; i++) {
     (void)hipSetDevice(p2p[i].comm->device);
@@ -290,6 +353,8 @@ ncclResult_t groupEndInternal(ncclSimInfo_t* simInfo) {
     r = collJoin(at);
     if (r == ncclSuccess) r = p2pOtherStreams(p2p[i], false);
   }
+  for (size_t i = 0; i < rma.size() && r == ncclSuccess; i++)
+    for (size_t j = 0; j < rma[i].streams.size() && r == ncclSuccess; j++) r = collJoin(rmaAt(rma[i], rma[i].streams[j]));
   (void)hipSetDevice(dev);
   return r;
 }

@@ -14,6 +14,13 @@ ncclResult_t launchKernGather(const LaunchPlan& p) {
 ncclResult_t launchP2pKernel(const ncclComm* comm, const P2pLaunch& l, hipStream_t stream) {
   return launchP2pT<>(comm, l, stream);
 }
+// ncclPutSignal / ncclSignal / ncclWaitSignal: bytes too (rma.cc)
+ncclResult_t launchRmaPutKernel(const ncclComm* comm, const RmaLaunch& l, hipStream_t stream) {
+  return launchRmaPutT<>(comm, l, stream);
+}
+ncclResult_t launchRmaWaitKernel(const ncclComm* comm, const RmaWaitArgs& w, hipStream_t stream) {
+  return launchRmaWaitT<>(comm, w, stream);
+}
 // Force this code object to load now (see warmKernels in kernels.hip).
 hipError_t warmKernGather() {
   hipFuncAttributes attr;

@@ -19,6 +19,8 @@
 //   llKernel   the LL protocol for small AllReduces and group batches (flag-in-data lines, no fences),
 //   symKernel  the zero-copy kernels for buffers in symmetric windows (peers' buffers pulled directly),
 //   p2pKernel  ncclSend / ncclRecv: one workgroup per (direction, peer, channel) over the pair's RS slots and credits,
+//   rmaPutKernel / rmaWaitKernel  ncclPutSignal / ncclSignal / ncclWaitSignal: stores straight into the peer's window,
+//              one posting wave per peer; one polling wave,
 //   oneRankKernel (PreMulSum at nRanks == 1; the nRanks == 1 copy lives in kernels.hip).
 //
 // Memory model: remote payload = `global_store_dwordx4 ... sc0 sc1` (system-scope
@@ -147,7 +149,7 @@ __device__ void reportError(const DevComm& dc, uint32_t code) {
 
 // Block-wide state kept in LDS.
 struct ChanState {
-  uint64_t ctr[CTR_KINDS][NCCL_AMD_MAX_RANKS];
+  uint64_t ctr[CTR_CHAN_KINDS][NCCL_AMD_MAX_RANKS];
   int abort;
 };
 
@@ -180,6 +182,21 @@ __device__ __forceinline__ bool probeMismatch(const WaitProbe& pr, int lane) {
   return ev;
 }
 
+// The slow path of every bounded spin (waitAll, the one-sided kernels): give up on the abort word, on an error another
+// workgroup recorded, on the timeout. Wave-uniform; lane 0 records the error.
+__device__ __forceinline__ bool spinGiveUp(const DevComm& dc, uint64_t t0, int lane) {
+  if (__hip_atomic_load(dc.abortFlag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) {
+    if (lane == 0) reportError(dc, DERR_ABORT);
+    return true;
+  }
+  if (__hip_atomic_load(dc.errorWord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) return true;
+  if (clockTicks() - t0 > dc.timeoutTicks) {
+    if (lane == 0) reportError(dc, DERR_TIMEOUT);
+    return true;
+  }
+  return false;
+}
+
 // Wave 0 waits until every selected flag word reaches its target (target[r] == 0: no wait on r).
 // ACQ: follow with a system-scope acquire (needed before reading data the flags publish; not for
 // credit/ack words, which guard no data). All threads must call it (it ends in a barrier).
@@ -204,17 +221,12 @@ __device__ bool waitAll(const DevComm& dc, ChanState& st, const uint64_t* flagBa
           __atomic_thread_fence(__ATOMIC_ACQUIRE);
           mismatch = loadFlag(flagBase + lane) < target[lane];  // still missing after the other kind's flag
         }
-        if (__hip_atomic_load(dc.abortFlag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) {
-          if (lane == 0) reportError(dc, DERR_ABORT);
-          bad = true;
-        } else if (__any(mismatch)) {
+        // an abort is reported before a mismatch; a mismatch before another workgroup's error or the timeout
+        if (__any(mismatch) && !__hip_atomic_load(dc.abortFlag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) {
           if (mismatch) reportError(dc, DERR_MISMATCH);
           bad = true;
-        } else if (__hip_atomic_load(dc.errorWord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) {
-          bad = true;  // another workgroup already failed: stop waiting
-        } else if (clockTicks() - t0 > dc.timeoutTicks) {
-          if (lane == 0) reportError(dc, DERR_TIMEOUT);
-          bad = true;
+        } else {
+          bad = spinGiveUp(dc, t0, lane);
         }
         if (bad) {
           if (lane == 0) st.abort = 1;
@@ -1142,7 +1154,7 @@ struct Channel {
 // Per-channel credit counters live in device memory between launches; a workgroup keeps them in LDS.
 __device__ __forceinline__ void loadCounters(const DevComm& dc, Shared& sh, int c) {
   const int tid = threadIdx.x;
-  if (tid < CTR_KINDS * NCCL_AMD_MAX_RANKS) {
+  if (tid < CTR_CHAN_KINDS * NCCL_AMD_MAX_RANKS) {
     int k = tid / NCCL_AMD_MAX_RANKS, r = tid % NCCL_AMD_MAX_RANKS;
     sh.st.ctr[k][r] = dc.counters[ctrIndex(c, k, r)];
   }
@@ -1156,7 +1168,7 @@ __device__ __forceinline__ void loadCounters(const DevComm& dc, Shared& sh, int 
 __device__ __forceinline__ void storeCounters(const DevComm& dc, Shared& sh, int c) {
   __syncthreads();
   const int tid = threadIdx.x;
-  if (tid < CTR_KINDS * NCCL_AMD_MAX_RANKS) {
+  if (tid < CTR_CHAN_KINDS * NCCL_AMD_MAX_RANKS) {
     int k = tid / NCCL_AMD_MAX_RANKS, r = tid % NCCL_AMD_MAX_RANKS;
     dc.counters[ctrIndex(c, k, r)] = sh.st.ctr[k][r];
   }
@@ -1334,6 +1346,120 @@ __global__ void __launch_bounds__(kThreads) kCoResident p2pKernel(P2pArgs<S, M> 
     }
   }
   if (tid == 0) *ctrWord = seq;
+}
+
+// ------------------------------------------------------------------------------------ one-sided put / signal / wait
+// ncclPutSignal / ncclSignal / ncclWaitSignal (rma.cc). A put stores straight into the peer's window
+// as mapped here: one copy, no slot, no credit, no wait on the remote rank. One launch serves a batch; per target peer
+// a stream of messages in issue order on a fixed set of workgroups, workgroup j of the stream copying part j of every
+// message. After a message's stores every storing wave drains, the workgroup barriers and one lane counts the
+// workgroup in on the peer's local arrival counter, and no workgroup starts message i + 1 before all have arrived for
+// message i (data in issue order). ONE wave — wave 0 of the stream's first workgroup — posts every
+// signal of the stream: once all of the stream's workgroups have arrived for message i it stores base + i + 1 into the
+// peer's signal word (a single writer: were each message's last arriver to post, two workgroups could store i + 2 and
+// i + 1 out of order). The word is monotonic, written by this rank alone and polled by its owner alone.
+template <int S, int M>
+__global__ void __launch_bounds__(kThreads) kCoResident rmaPutKernel(RmaArgs<S, M> a) {
+  const DevComm& dc = *a.comm;
+  const int tid = threadIdx.x, me = dc.rank;
+  int si = 0;
+  for (int i = 1; i < a.nStreams && i < S; i++)
+    if ((int)blockIdx.x >= (int)a.st[i].wgOff) si = i;  // streams in workgroup order
+  const RmaStream sd = a.st[si];
+  const int j = (int)blockIdx.x - (int)sd.wgOff;
+  const int peer = sd.peer;
+  // malformed arguments (the host's grid check refuses them first): touch nothing
+  if (j < 0 || j >= (int)sd.nch || peer >= dc.nRanks || (int)sd.msgOff + (int)sd.nMsgs > M) return;
+  const bool noRel = (a.protoFlags & 8) != 0;
+  uint64_t* const arrive = dc.counters + ctrIndex(0, CTR_SIG_ARRIVE, peer);
+  uint64_t* const sentWord = dc.counters + ctrIndex(0, CTR_SIG_SENT, peer);
+  uint64_t* const sigWord = dc.flags[peer] + flagIndex(0, FLG_SIGNAL, me);
+  const bool wave0 = tid < 64;
+  const bool poster = j == 0 && wave0;
+  const uint64_t base = poster ? *sentWord : 0;
+  bool ok = true;
+  for (int m = 0; m < (int)sd.nMsgs; m++) {
+    const RmaMsg msg = a.msg[(int)sd.msgOff + m];
+    if (j < (int)msg.nch) {
+      uint64_t lo, hi;
+      sliceBounds(msg.part, msg.part, j, 0, msg.bytes, lo, hi);  // part j: a multiple of 16 bytes from the start
+      const bool aligned = ((msg.src | msg.dst) & 15) == 0 && !a.elementwise;
+      copyRange<uint8_t, true>((char*)msg.dst + lo, (const char*)msg.src + lo, hi - lo, aligned);
+    }
+    // a workgroup with no bytes in this message arrives too: the count per message is the stream's workgroups
+    drainStores();
+    __syncthreads();
+    if (tid == 0) {
+      if (!noRel) {
+        __atomic_thread_fence(__ATOMIC_RELEASE);
+        drainStores();
+      }
+      __hip_atomic_fetch_add(arrive, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const bool last = m + 1 == (int)sd.nMsgs;
+    // Message m + 1 starts, and message m's signal is posted, only once EVERY workgroup of the stream has arrived for
+    // message m: wave 0 of each workgroup waits on the local counter for the full count (the last message: only the
+    // posting wave), the barrier below holds the other waves. So the stream's messages reach the peer in issue order —
+    // of two puts to overlapping bytes the later one's data stays — and the count is exact: no workgroup adds for
+    // message m + 1 before all have added for m. The workgroups of a launch are co-resident (grid <= chanCap).
+    if (wave0 && ok && (poster || !last)) {
+      const uint64_t want = (uint64_t)(m + 1) * sd.nch;
+      uint64_t t0 = 0;
+      uint32_t iter = 0;
+      while (__hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
+        if (iter == 0) t0 = clockTicks();
+        __builtin_amdgcn_s_sleep(1);
+        if ((++iter & 255) == 0 && spinGiveUp(dc, t0, tid)) {
+          ok = false;  // the communicator is in error: the counter is left as it is, nothing more is ordered or posted
+          break;
+        }
+      }
+      if (poster && ok && tid == 0) {
+        if (!noRel) {
+          __atomic_thread_fence(__ATOMIC_RELEASE);
+          drainStores();
+        }
+        storeFlag(sigWord, base + (uint64_t)m + 1);
+      }
+    }
+    if (!last) __syncthreads();
+  }
+  // every workgroup of the stream has arrived for the last message (the poster saw the full count), so none adds any
+  // more: the arrival counter goes back to zero for the next launch, the sent counter forward by the signals posted.
+  // (Not after a spin gave up: the error is sticky and no later launch of this communicator is admitted.)
+  if (poster && ok && tid == 0) {
+    *sentWord = base + sd.nMsgs;
+    __hip_atomic_store(arrive, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// ncclWaitSignal: one wave; lane i polls this rank's signal word of peer d[i].peer for consumed + opCnt, with the
+// bounded spin of waitAll. Once every lane is satisfied: one system-scope acquire, then the consumed counters move.
+template <int WAVE = 64>
+__global__ void __launch_bounds__(WAVE) rmaWaitKernel(RmaWaitArgs a) {
+  const DevComm& dc = *a.comm;
+  const int lane = threadIdx.x;
+  const bool need = lane < a.n && lane < NCCL_AMD_MAX_RANKS && a.d[lane].peer >= 0 && a.d[lane].peer < dc.nRanks;
+  const int peer = need ? a.d[lane].peer : 0;
+  uint64_t* const seenWord = dc.counters + ctrIndex(0, CTR_SIG_SEEN, peer);
+  const uint64_t* const sigWord = dc.flags[dc.rank] + flagIndex(0, FLG_SIGNAL, peer);
+  const uint64_t target = need ? *seenWord + a.d[lane].opCnt : 0;
+  uint64_t t0 = 0;
+  uint32_t iter = 0;
+  bool good = true;
+  while (true) {
+    const bool ok = !need || loadFlag(sigWord) >= target;
+    if (__all(ok)) break;
+    if (iter == 0) t0 = clockTicks();
+    __builtin_amdgcn_s_sleep(1);
+    if ((++iter & 255) == 0 && spinGiveUp(dc, t0, lane)) {
+      good = false;
+      break;
+    }
+  }
+  if (!good) return;  // nothing consumed: the communicator is in error
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);  // buffer_inv sc0 sc1: the puts' bytes, for whatever the stream runs next
+  if (need) *seenWord = target;
 }
 
 }  // namespace ncclamd
@@ -2263,6 +2389,37 @@ inline ncclResult_t launchP2pT(const ncclComm* comm, const P2pLaunch& l, hipStre
   if (l.streams.size() > (size_t)kP2pMaxStreams || l.msgs.size() > (size_t)kP2pMaxMsgs || l.grid < 1) return ncclInternalError;
   if (l.streams.size() <= (size_t)SMALL && l.msgs.size() <= (size_t)SMALL) launchP2pArgs<SMALL, SMALL>(comm, l, stream);
   else launchP2pArgs<kP2pMaxStreams, kP2pMaxMsgs>(comm, l, stream);
+  HIPCHECK(hipGetLastError());
+  return ncclSuccess;
+}
+
+// One rmaPutKernel launch, a lone put or signal with the small argument block (as launchP2pT), and the wait kernel
+template <int S, int M>
+inline void launchRmaPutArgs(const ncclComm* comm, const RmaLaunch& l, hipStream_t stream) {
+  RmaArgs<S, M> a;
+  __builtin_memset(&a, 0, sizeof(a));
+  a.comm = comm->devComm;
+  a.nStreams = (int)l.streams.size();
+  a.protoFlags = comm->tune.protoFlags;
+  a.elementwise = comm->tune.forceElementwise;
+  for (size_t i = 0; i < l.streams.size(); i++) a.st[i] = l.streams[i];
+  for (size_t i = 0; i < l.msgs.size(); i++) a.msg[i] = l.msgs[i];
+  NCCL_AMD_LAUNCH((rmaPutKernel<S, M>), dim3(l.grid), dim3(kThreads), 0, stream, a);
+}
+template <int SMALL = 1>
+inline ncclResult_t launchRmaPutT(const ncclComm* comm, const RmaLaunch& l, hipStream_t stream) {
+  if (l.streams.size() > (size_t)kRmaMaxStreams || l.msgs.size() > (size_t)kRmaMaxMsgs || l.grid < 1) return ncclInternalError;
+  if (l.streams.size() <= (size_t)SMALL && l.msgs.size() <= (size_t)SMALL) launchRmaPutArgs<SMALL, SMALL>(comm, l, stream);
+  else launchRmaPutArgs<kRmaMaxStreams, kRmaMaxMsgs>(comm, l, stream);
+  HIPCHECK(hipGetLastError());
+  return ncclSuccess;
+}
+template <int WAVE = 64>
+inline ncclResult_t launchRmaWaitT(const ncclComm* comm, const RmaWaitArgs& w, hipStream_t stream) {
+  if (w.n < 1 || w.n > NCCL_AMD_MAX_RANKS) return ncclInternalError;
+  RmaWaitArgs a = w;
+  a.comm = comm->devComm;
+  NCCL_AMD_LAUNCH((rmaWaitKernel<WAVE>), dim3(1), dim3(WAVE), 0, stream, a);
   HIPCHECK(hipGetLastError());
   return ncclSuccess;
 }

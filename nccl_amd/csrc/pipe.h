@@ -186,7 +186,7 @@ __global__ void __launch_bounds__(kThreads) kCoResident pipeKernel(CollArgs a) {
   __shared__ PipeShared sh;
   const DevComm& dc = *a.comm;
   const int tid = threadIdx.x, c = blockIdx.x, me = dc.rank, n = dc.nRanks;
-  if (tid < CTR_KINDS * NCCL_AMD_MAX_RANKS) {
+  if (tid < CTR_CHAN_KINDS * NCCL_AMD_MAX_RANKS) {
     int k = tid / NCCL_AMD_MAX_RANKS, r = tid % NCCL_AMD_MAX_RANKS;
     sh.st.ctr[k][r] = dc.counters[ctrIndex(c, k, r)];
   }
@@ -321,7 +321,7 @@ __global__ void __launch_bounds__(kThreads) kCoResident pipeKernel(CollArgs a) {
     }
   }
   __syncthreads();
-  if (tid < CTR_KINDS * NCCL_AMD_MAX_RANKS) {
+  if (tid < CTR_CHAN_KINDS * NCCL_AMD_MAX_RANKS) {
     int k = tid / NCCL_AMD_MAX_RANKS, r = tid % NCCL_AMD_MAX_RANKS;
     dc.counters[ctrIndex(c, k, r)] = sh.st.ctr[k][r];
   }

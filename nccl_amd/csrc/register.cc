@@ -108,6 +108,7 @@ static ncclResult_t windowRegister(ncclComm* comm, void* buff, size_t size, nccl
   w->flags = flags;
   for (int r = 0; r < comm->nRanks; r++) {
     const WinInfo& p = all[r];
+    w->peerSize[r] = (size_t)p.size;
     if ((p.flags & NCCL_WIN_COLL_SYMMETRIC) != (flags & NCCL_WIN_COLL_SYMMETRIC) || p.size != size) {
       if (flags & NCCL_WIN_COLL_SYMMETRIC)
         INFO("window %p: rank %d registered size %lu flags %d (mine %zu / %d): not symmetric", buff, r,

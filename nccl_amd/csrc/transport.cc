@@ -49,7 +49,20 @@ size_t commDeviceBytes(const ncclComm* c) {
 
 ncclResult_t transportSetup(ncclComm* comm) {
   HIPCHECK(hipSetDevice(comm->device));
-  if (comm->nRanks == 1) return ncclSuccess;  // nranks==1 never touches peers (onerank.cu:49-110)
+  if (comm->nRanks == 1) {
+    // nranks==1 never touches peers (onerank.cu:49-110): no staging, no LL lines. Only channel 0's flag words, for the
+    // signal a rank raises for itself (ncclPutSignal / ncclSignal with peer == rank, rma.cc)
+    const size_t fb = (size_t)FLG_KINDS * NCCL_AMD_MAX_RANKS * sizeof(uint64_t);
+    {
+      std::lock_guard<std::mutex> mapLock(ipcMapMutex());
+      HIPCHECK(hipExtMallocWithFlags((void**)&comm->flags, fb, hipDeviceMallocUncached));
+    }
+    comm->flagsAllocBytes = fb;
+    HIPCHECK(hipMemset(comm->flags, 0, fb));
+    HIPCHECK(hipDeviceSynchronize());
+    comm->peerFlags[0] = comm->flags;
+    return ncclSuccess;
+  }
   size_t sb = stagingBytes(comm), fb = flagsBytes(comm);
   {
     // only the allocations themselves are serialized with imports / releases (gMapMu): the fd server thread
