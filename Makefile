@@ -24,7 +24,7 @@ HDRS     := $(wildcard $(SRCDIR)/*.h) include/nccl.h
 
 all: lib oracle numerics-host bootstrap-test tuner-test nccl-perf comm-examples plan-test mapcheck-test xgmi-probe atomicity-probe \
      fp8-probe release-probe reuse-probe export-check-test barrier-probe bcast-plan-test bcast-example p2p-plan-test sendrecv-example \
-     rma-plan-test
+     rma-plan-test sym-a2a-plan-test
 
 .PHONY: export-check-test
 export-check-test: tests/native/export_check_test
@@ -157,6 +157,16 @@ tests/native/rma_plan_test: tests/native/rma_plan_test.cc $(SRCDIR)/rma.cc $(SRC
 	  $(SRCDIR)/rma.cc $(SRCDIR)/group.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
 
 .PHONY: rma-plan-test
+
+# CPU sweep of the cut the zero-copy AlltoAll / Gather kernel walks (device_abi.h symA2ACut / symA2APart): a stand-alone
+# host program, built under ASan+UBSan (host code only)
+sym-a2a-plan-test: tests/native/sym_a2a_plan_test
+
+tests/native/sym_a2a_plan_test: tests/native/sym_a2a_plan_test.cc $(SRCDIR)/device_abi.h
+	$(CXX) -g -O1 -fno-omit-frame-pointer -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude \
+	  -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
+
+.PHONY: sym-a2a-plan-test
 
 # a C-ABI caller of ncclSend / ncclRecv / ncclAlltoAll written against include/nccl.h only (links with -lnccl alone)
 sendrecv-example: tests/native/sendrecv_example

@@ -506,7 +506,8 @@ class Communicator:
                       _stream_ptr(stream, self.device))
 
     def alltoall(self, sendbuf, recvbuf, *, stream=None) -> None:
-        """Block j of sendbuf goes to rank j; block i of recvbuf comes from rank i (nranks equal blocks each)."""
+        """Block j of sendbuf goes to rank j; block i of recvbuf comes from rank i (nranks equal blocks each). With
+        sendbuf inside a WIN_COLL_SYMMETRIC window (the same offset on every rank) the call runs zero-copy."""
         self._check_tensors("alltoall", sendbuf, recvbuf)
         if sendbuf.numel() != recvbuf.numel() or sendbuf.dtype != recvbuf.dtype or sendbuf.numel() % self.nranks:
             raise ValueError("alltoall: sendbuf/recvbuf must match in dtype and hold nranks equal blocks")
@@ -514,7 +515,8 @@ class Communicator:
                           torch_dtype_to_nccl(sendbuf.dtype), _stream_ptr(stream, self.device))
 
     def gather(self, sendbuf, recvbuf, root: int = 0, *, stream=None) -> None:
-        """The root's recvbuf := every rank's sendbuf, rank i's at block i (recvbuf is used on the root only)."""
+        """The root's recvbuf := every rank's sendbuf, rank i's at block i (recvbuf is used on the root only). With
+        sendbuf inside a WIN_COLL_SYMMETRIC window (the same offset on every rank) the call runs zero-copy."""
         self._check_tensors("gather", sendbuf, recvbuf if self.rank == root else None)
         if self.rank == root and (recvbuf is None or recvbuf.numel() != sendbuf.numel() * self.nranks
                                   or recvbuf.dtype != sendbuf.dtype):

@@ -240,7 +240,10 @@ struct RegHandle {  // what ncclCommRegister returns
 // FUNC_KINDS sizes the per-collective tables.
 enum CollFunc {
   FUNC_ALLREDUCE = 0, FUNC_REDUCESCATTER = 1, FUNC_ALLGATHER = 2, FUNC_REDUCE = 3, FUNC_COUNT = 4,
-  FUNC_BROADCAST = 4, FUNC_KINDS = 5
+  FUNC_BROADCAST = 4, FUNC_KINDS = 5,
+  // ncclAlltoAll / ncclGather whose sendbuff lies in a symmetric window (p2p.cc): planned and launched as collectives
+  // on symA2AKernel. No row in the per-collective tables: NCCL_ALGO, NCCL_PROTO and the tuner plugin are not consulted.
+  FUNC_SYM_ALLTOALL = 5, FUNC_SYM_GATHER = 6
 };
 
 // One collective's NCCL_ALGO / NCCL_PROTO enables (reference: the algoEnable / protoEnable rows of
@@ -265,6 +268,7 @@ struct CommTuning {
   FuncTuning fn[FUNC_KINDS];  // NCCL_ALGO / NCCL_PROTO per collective (reference grammar, enqueue.cc parseEnableList)
   int parseError;           // nonzero: NCCL_ALGO / NCCL_PROTO did not parse; every rank's init fails (ncclInvalidUsage)
   int symDisable;          // NCCL_AMD_SYM_DISABLE
+  int symA2A;               // NCCL_AMD_SYM_A2A: AlltoAll / Gather with the sendbuff in a symmetric window run zero-copy
   int symOneShot;           // NCCL_AMD_SYM_ONESHOT: caller promises out-of-place window AllReduces
   int symWtPublish;         // NCCL_AMD_SYM_WT: symmetric kernels publish with write-through stores, no L2 write-back
   int localRegister;        // NCCL_LOCAL_REGISTER: ncclCommRegister maps buffers into peers (zero-copy collectives)
@@ -506,11 +510,15 @@ struct SymPlan {  // one symmetric (window) kernel launch
   int nChannels;
   hipStream_t stream;
   SymArgs args;
+  SymA2AArgs a2a;       // coll SYM_A2A / SYM_GATHER: symA2AKernel's arguments (args unused)
   RegAlloc* regUse[2];  // registered mode: the send / recv registrations it runs on (their lastEv, register.cc)
   bool bounced;         // runs on the bounce allocation: `bounce` copies around the launch (bounceLaunch)
   BounceCopy bounce;
 };
 ncclResult_t launchSymPlan(const SymPlan& plan);  // kernels.hip
+// ncclAlltoAll / ncclGather (p2p.cc): does this call take the zero-copy plan? From what every rank shares and this
+// rank's sendbuff alone (a symmetric window holds it on every rank or on none) — never from recvbuff, rank or root.
+bool symA2AEligible(ncclComm* comm, const void* sendbuff, size_t sendBytes, size_t count);  // enqueue.cc
 
 // planColl's outcome: a kernel launch (LaunchPlan), a symmetric-window launch (SymPlan) or nothing
 enum PlanKind { PLAN_KERNEL = 0, PLAN_SYM = 1, PLAN_NONE = 2 };

@@ -267,6 +267,45 @@ __host__ __device__ inline int p2pSteps(uint64_t bytes, uint64_t part, uint64_t 
   return (int)((hi - lo + slice - 1) / slice);
 }
 
+// ---- zero-copy AlltoAll / Gather on symmetric windows (kernels.h symA2AKernel, enqueue.cc) ----
+// Every rank block of B bytes is cut alike, from B and rank-uniform constants alone (the function is not given the
+// rank, so every rank launches the same grid): nch = clamp(ceil(B / minChannelBytes), max(minCTAs, 1), cap) channels
+// of alignUp(ceil(B / nch), 16) bytes; channel c owns bytes [min(c * part, B), min((c + 1) * part, B)) of EVERY
+// block. A channel whose range is empty still runs the handshake (the channels' epochs stay in step).
+// Host-callable so that tests/native/sym_a2a_plan_test walks exactly what the kernel walks.
+struct SymA2ACut {
+  int nch;
+  uint64_t part;
+};
+__host__ __device__ inline SymA2ACut symA2ACut(uint64_t bytes, uint64_t minChannelBytes, int minCTAs, int cap) {
+  if (minChannelBytes < 16) minChannelBytes = 16;
+  uint64_t nch = (bytes + minChannelBytes - 1) / minChannelBytes;
+  if (nch < (uint64_t)(minCTAs > 1 ? minCTAs : 1)) nch = (uint64_t)(minCTAs > 1 ? minCTAs : 1);
+  if (nch > (uint64_t)(cap > 1 ? cap : 1)) nch = (uint64_t)(cap > 1 ? cap : 1);
+  SymA2ACut c;
+  c.nch = (int)nch;
+  c.part = ((bytes + nch - 1) / nch + 15) / 16 * 16;
+  return c;
+}
+__host__ __device__ inline void symA2APart(uint64_t part, int c, uint64_t bytes, uint64_t& lo, uint64_t& hi) {
+  lo = minU64((uint64_t)c * part, bytes);
+  hi = minU64(lo + part, bytes);
+}
+enum SymA2AMode { SYM_A2A_ALLTOALL = 0, SYM_A2A_GATHER = 1 };
+// Kernel arguments: every rank's sendbuff as mapped in this process (the same offset in every rank's window) and
+// this rank's recvbuff, which needs no window (only sendbuffs are read remotely; GATHER: used on the root only).
+struct SymA2AArgs {
+  const DevComm* comm;
+  const char* send[NCCL_AMD_MAX_RANKS];
+  char* recv;
+  uint64_t bytes;   // B: bytes per rank block
+  uint64_t part;    // bytes per channel within a block (symA2ACut)
+  int mode;         // SymA2AMode
+  int root;         // GATHER
+  int elementwise;  // NCCL_AMD_FORCE_ELEMENTWISE
+  int pad;
+};
+
 // One message of a stream, and one stream = the in-order messages of one group to (recv == 0) or from one peer.
 // Stream i runs on workgroups wgOff .. wgOff + nch - 1 of its launch, workgroup wgOff + j on physical channel j, which
 // walks the stream's messages in order and skips those cut into j or fewer parts.

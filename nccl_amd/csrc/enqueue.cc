@@ -226,6 +226,9 @@ void loadTuning(CommTuning* t) {
     }
   }
   t->symDisable = (int)paramInt("NCCL_AMD_SYM_DISABLE", 0);
+  // ncclAlltoAll / ncclGather whose sendbuff lies in a symmetric window pull straight from the peers' windows
+  // (symA2AKernel); 0: the staged send / recv expansion whatever the buffers are
+  t->symA2A = (int)paramInt("NCCL_AMD_SYM_A2A", 1);
   t->symOneShot = (int)paramInt("NCCL_AMD_SYM_ONESHOT", 0);
   // write-through publish in the symmetric kernels: n = 2 one-GPU rehearsal 0.291-0.295 -> 0.234-0.241 ms at
   // 256 MiB fp32 (no per-channel L2 write-back; profiles/r02_sym_wt_ab_onegpu.txt)
@@ -701,11 +704,63 @@ static bool eagerOn(const ncclComm* comm) {
   return comm->tune.eagerRegister > 0 || (comm->tune.eagerRegister < 0 && comm->multiProcess && comm->regIpcAll);
 }
 
+// Zero-copy AlltoAll / Gather (kernels.h symA2AKernel). Every rank makes the same call, so every rank
+// decides alike from what all ranks share (n, count, the agreed knobs) and from its own sendbuff, which lies in a
+// symmetric window on every rank or on none (same-offset contract of the other symmetric plans). Never from recvbuff
+// (no peer reads it; a Gather non-root's is unused), the rank or the root: that would split the kernel kinds.
+bool symA2AEligible(ncclComm* comm, const void* sendbuff, size_t sendBytes, size_t count) {
+  return comm->nRanks >= 2 && count > 0 && !comm->tune.symDisable && comm->tune.symA2A != 0 &&
+         findSymWindow(comm, sendbuff, sendBytes) != nullptr;
+}
+
+// The channel cap of a symA2AKernel launch: the co-resident cap and, at n >= 3, the CU budget of the other symmetric
+// plans (linkChannels)
+static int symA2AChannelCap(const ncclComm* comm) {
+  int cap = comm->chanCap;
+  if (comm->nRanks >= 3 && comm->tune.linkChannels > 0) cap = std::min(cap, comm->tune.linkChannels);
+  return cap;
+}
+
+static ncclResult_t planSymA2A(const CollInfo& info, SymPlan& sp, int* kind) {
+  ncclComm* comm = info.comm;
+  const int n = comm->nRanks;
+  const bool gather = info.func == FUNC_SYM_GATHER;
+  const size_t B = info.count * (size_t)typeSize(info.datatype);
+  ncclWindow_vidmem* ws = n >= 2 && B > 0 ? findSymWindow(comm, info.sendbuff, gather ? B : (size_t)n * B) : nullptr;
+  if (!ws) {  // (the entry point asked symA2AEligible; a window deregistered inside the group since)
+    WARN("%s: the symmetric window that held sendbuff %p at the call is gone", info.opName, info.sendbuff);
+    return ncclInvalidUsage;
+  }
+  comm->opCount++;
+  *kind = PLAN_SYM;
+  memset(&sp, 0, sizeof(sp));
+  sp.coll = gather ? 5 /*SYM_GATHER*/ : 4 /*SYM_A2A*/;
+  sp.datatype = ncclInt8;  // bytes
+  sp.eltSize = 1;
+  sp.stream = info.stream;
+  SymA2AArgs& a = sp.a2a;
+  a.comm = comm->devComm;
+  for (int r = 0; r < n; r++) a.send[r] = ws->peerPtr[r] + ((const char*)info.sendbuff - (const char*)ws->userPtr);
+  a.send[comm->rank] = (const char*)info.sendbuff;
+  a.recv = (char*)info.recvbuff;
+  a.bytes = B;
+  a.mode = gather ? SYM_A2A_GATHER : SYM_A2A_ALLTOALL;
+  a.root = info.root;
+  a.elementwise = comm->tune.forceElementwise;
+  const SymA2ACut cut = symA2ACut(B, (uint64_t)std::max<int64_t>(1, comm->tune.minChannelBytes), comm->minCTAs,
+                                  symA2AChannelCap(comm));
+  a.part = cut.part;
+  sp.nChannels = cut.nch;
+  TRACE("%s: symmetric nch %d part %lu bytes %zu root %d", info.opName, cut.nch, (unsigned long)cut.part, B, info.root);
+  return ncclSuccess;
+}
+
 ncclResult_t planColl(const CollInfo& info, LaunchPlan& p, SymPlan& sp, int* kind) {
   ncclComm* comm = info.comm;
   const int ts = typeSize(info.datatype);
   memset(&p, 0, sizeof(p));
   *kind = PLAN_KERNEL;
+  if (info.func == FUNC_SYM_ALLTOALL || info.func == FUNC_SYM_GATHER) return planSymA2A(info, sp, kind);
   p.func = info.func;
   p.datatype = info.datatype;
   p.eltSize = ts;

@@ -9,6 +9,8 @@
 // the node even without a group — the group is still honoured for ordering and error reporting.
 // ncclSend / ncclRecv (p2p.cc) are recorded beside the collectives; at the group end each communicator's p2p work is
 // planned first (errors before anything launches) and launched after the group's collectives.
+// A zero-copy ncclAlltoAll / ncclGather (sendbuff in a symmetric window) is recorded as a collective and
+// launches in the collectives' section, in issue order.
 // The one-sided operations (rma.cc) likewise: planned first, launched per communicator in issue order after that
 // communicator's collectives and p2p launches.
 #include <string.h>
@@ -132,6 +134,9 @@ static ModelCost planCost(const PlannedColl& pc) {
   const int n = comm->nRanks;
   size_t bytes = pc.info.count * (size_t)typeSize(pc.info.datatype);
   if (pc.info.func == FUNC_REDUCESCATTER || pc.info.func == FUNC_ALLGATHER) bytes *= (size_t)n;
+  // zero-copy AlltoAll / Gather: the symmetric model on the bytes a rank pulls — n blocks in the model's terms, which
+  // prices (n-1)/n of them on the links, i.e. (n-1) B (a Gather: its root's share, the launch's longest)
+  if (pc.info.func == FUNC_SYM_ALLTOALL || pc.info.func == FUNC_SYM_GATHER) bytes *= (size_t)n;
   ModelAlgo a = MODEL_DIRECT;
   if (pc.kind == PLAN_SYM) a = MODEL_SYM;
   else switch (pc.p.algo) {

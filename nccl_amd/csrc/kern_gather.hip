@@ -21,6 +21,8 @@ ncclResult_t launchRmaPutKernel(const ncclComm* comm, const RmaLaunch& l, hipStr
 ncclResult_t launchRmaWaitKernel(const ncclComm* comm, const RmaWaitArgs& w, hipStream_t stream) {
   return launchRmaWaitT<>(comm, w, stream);
 }
+// zero-copy ncclAlltoAll / ncclGather on symmetric windows: bytes as well (enqueue.cc planSymA2A)
+ncclResult_t launchSymA2AKernel(const SymPlan& p) { return launchSymA2AT<>(p); }
 // Force this code object to load now (see warmKernels in kernels.hip).
 hipError_t warmKernGather() {
   hipFuncAttributes attr;

@@ -18,6 +18,7 @@
 // Besides this staged kernel (collKernel, with its one-shot variant COLL_AR1) the file holds
 //   llKernel   the LL protocol for small AllReduces and group batches (flag-in-data lines, no fences),
 //   symKernel  the zero-copy kernels for buffers in symmetric windows (peers' buffers pulled directly),
+//   symA2AKernel  ncclAlltoAll / ncclGather with the sendbuff in a symmetric window (one pulled copy per byte),
 //   p2pKernel  ncclSend / ncclRecv: one workgroup per (direction, peer, channel) over the pair's RS slots and credits,
 //   rmaPutKernel / rmaWaitKernel  ncclPutSignal / ncclSignal / ncclWaitSignal: stores straight into the peer's window,
 //              one posting wave per peer; one polling wave,
@@ -2080,7 +2081,8 @@ __global__ void __launch_bounds__(kThreads) kCoResident llKernel(LLArgs<K> a) {
 // system-scope acquire. Link bytes are those of the staged path, local HBM traffic drops from
 // 2S + 4(n-1)S/n to about 3S, and one handshake round replaces the per-slice credit protocol.
 // The epoch of each channel lives in device memory (counters[c][CTR_SYM]), so graphs replay.
-enum SymColl { SYM_AR = 0, SYM_AR1 = 1, SYM_RS = 2, SYM_AG = 3 };
+// SYM_A2A / SYM_GATHER are SymPlan::coll values only: they run symA2AKernel below, not a symKernel instantiation.
+enum SymColl { SYM_AR = 0, SYM_AR1 = 1, SYM_RS = 2, SYM_AG = 3, SYM_A2A = 4, SYM_GATHER = 5 };
 
 struct SymShared {
   ChanState st;
@@ -2283,6 +2285,63 @@ template <typename T>
 inline ncclResult_t launchSymIntOp(const SymPlan& p) {
   if (p.devOp == DEV_SUMPOSTDIV) return launchSymTyped<T, DEV_SUMPOSTDIV>(p);
   return launchSymOp<T>(p);
+}
+
+// Zero-copy AlltoAll / Gather: every rank's sendbuff lies at the same offset of a symmetric window,
+// so rank r PULLS block r of every peer's sendbuff (Gather: the root pulls every peer's one block) straight into its
+// recvbuff. One copy per byte, one ENTER / DONE round per channel in place of the staged path's per-slice credits.
+//   self   my own block is copied locally before any wait;
+//   ENTER  as symKernel's: a peer's kernel has started, so the kernels that wrote its sendbuff have finished;
+//   pull   peers in the channel-rotated order; remote loads, local stores — the section's invariant holds: no user
+//          buffer is written remotely;
+//   DONE   every peer has finished reading my sendbuff: the stream may overwrite it.
+// Bytes, one instantiation (kern_gather.hip). Every rank runs the whole round on every channel of the launch in both
+// modes — a Gather's non-roots and channels whose part is empty included — so the channels' epochs stay in step with
+// the other symmetric kernels'. The access width is decided per copied part by the rank that copies it, from the two
+// addresses: 16-byte packs when both are 16-byte aligned (parts start at multiples of 16 within a block), bytes else.
+// (A template only so that the one unit that launches it, kern_gather.hip, holds its code; the mode is a runtime field.)
+template <int UNIT = 0>
+__global__ void __launch_bounds__(kThreads) kCoResident symA2AKernel(SymA2AArgs a) {
+  __shared__ SymShared sh;
+  const DevComm& dc = *a.comm;
+  const int tid = threadIdx.x, c = blockIdx.x, me = dc.rank, n = dc.nRanks;
+  if (c >= dc.maxChannels) return;  // (the host's grid check refuses such a launch first)
+  if (tid == 0) sh.st.abort = 0;
+  const uint64_t e = dc.counters[ctrIndex(c, CTR_SYM, 0)] + 1;
+  const uint64_t B = a.bytes;
+  const bool gather = a.mode == SYM_A2A_GATHER;
+  const bool reader = !gather || me == a.root;
+  uint64_t lo, hi;
+  symA2APart(a.part, c, B, lo, hi);
+  auto pull = [&](int q) {
+    // block `me` of rank q's sendbuff (Gather: its only block) -> block q of my recvbuff
+    const char* src = a.send[q] + (gather ? 0 : (uint64_t)me * B);
+    char* dst = a.recv + (uint64_t)q * B;
+    if (dst == src || hi == lo) return;  // in place (Gather at the root: sendbuff == recvbuff + root * count)
+    const bool aligned = !a.elementwise && (((uintptr_t)dst | (uintptr_t)src) & 15) == 0;
+    copyRange<uint8_t, false>(dst + lo, src + lo, hi - lo, aligned);
+  };
+  if (reader) pull(me);
+  symSignal(dc, sh, c, FLG_SYM_ENTER, e, false);
+  bool ok = symWait(dc, sh, c, FLG_SYM_ENTER, e, true);
+  if (ok && reader) {
+    for (int k = 1; k < n; k++) pull(chanPeer(me, n, c, k));
+    __syncthreads();
+  }
+  if (ok) {
+    symSignal(dc, sh, c, FLG_SYM_DONE, e, false);  // drained: I no longer read any peer's sendbuff
+    ok = symWait(dc, sh, c, FLG_SYM_DONE, e, false);
+  }
+  (void)ok;  // on failure the error word is set and the epoch still advances (the comm is unusable)
+  if (tid == 0) dc.counters[ctrIndex(c, CTR_SYM, 0)] = e;
+}
+
+template <int UNIT = 0>
+inline ncclResult_t launchSymA2AT(const SymPlan& p) {
+  if (p.nChannels < 1) return ncclInternalError;
+  NCCL_AMD_LAUNCH((symA2AKernel<UNIT>), dim3(p.nChannels), dim3(kThreads), 0, p.stream, p.a2a);
+  HIPCHECK(hipGetLastError());
+  return ncclSuccess;
 }
 
 // ------------------------------------------------------------------------------------ nRanks == 1

@@ -27,6 +27,7 @@ ncclResult_t launchSymKernF32(const SymPlan& p);
 ncclResult_t launchSymKernF64(const SymPlan& p);
 ncclResult_t launchSymKernFp8(const SymPlan& p);
 ncclResult_t launchSymKernGather(const SymPlan& p);
+ncclResult_t launchSymA2AKernel(const SymPlan& p);
 hipError_t warmKernU8();
 hipError_t warmKernU32();
 hipError_t warmKernU64();
@@ -220,6 +221,7 @@ ncclResult_t launchPlan(const LaunchPlan& p) {
 }
 
 ncclResult_t launchSymPlan(const SymPlan& p) {
+  if (p.coll == SYM_A2A || p.coll == SYM_GATHER) return launchSymA2AKernel(p);
   if (p.coll == SYM_AG) return launchSymKernGather(p);
   switch (p.datatype) {
     case ncclInt8: case ncclUint8: return launchSymKernU8(p);

@@ -13,6 +13,9 @@
 // contiguous runs of the reference's rounds (round r: send to rank + r, recv from rank - r), a round's two streams
 // never apart. The unfinished stream of the smallest round anywhere then has every earlier launch of both its ranks
 // complete, so both its workgroups are resident: no deadlock, however each rank packs its rounds.
+//
+// ncclAlltoAll / ncclGather whose sendbuff lies in a symmetric window do not expand: they are planned and launched as
+// one collective on the zero-copy kernel (symA2ASubmit below, enqueue.cc planSymA2A).
 #include <string.h>
 
 #include <algorithm>
@@ -204,6 +207,15 @@ static ncclResult_t p2pSubmit(const P2pOp* ops, size_t nOps) {
   return own ? groupEndInternal() : ncclSuccess;
 }
 
+// AlltoAll / Gather with the sendbuff in a symmetric window (enqueue.cc symA2AEligible): one collective on the zero-copy
+// kernel instead of the send / recv expansion. Inside a group it is deferred with the group's
+// collectives and launches in their section, in issue order; outside it launches before the call returns.
+static ncclResult_t symA2ASubmit(const CollInfo& info) {
+  if (groupActive()) return groupDeferColl(info);
+  DeviceRestore restore;
+  return launchColl(info);
+}
+
 static ncclResult_t sendRecv(const char* opName, bool recv, void* buff, size_t count, ncclDataType_t datatype, int peer,
                              ncclComm* comm, hipStream_t stream) {
   ROCTX_RANGE("nccl%s comm=%p count=%zu datatype=%d peer=%d", opName, (void*)comm, count, (int)datatype, peer);
@@ -247,6 +259,8 @@ NCCL_EXPORT ncclResult_t ncclAlltoAll(const void* sendbuff, void* recvbuff, size
   INFO("AlltoAll: opCount %lx sendbuff %p recvbuff %p count %zu datatype %d comm %p [nranks=%d] stream %p",
        (unsigned long)comm->opCount, sendbuff, recvbuff, count, (int)datatype, (void*)comm, comm->nRanks, (void*)stream);
   const size_t bytes = count * (size_t)ts;
+  if (symA2AEligible(comm, sendbuff, (size_t)comm->nRanks * bytes, count))
+    return symA2ASubmit({FUNC_SYM_ALLTOALL, "AlltoAll", sendbuff, recvbuff, count, datatype, ncclSum, 0, comm, stream});
   std::vector<P2pOp> ops;
   for (int r = 0; r < comm->nRanks; r++) {
     ops.push_back({comm, stream, (char*)sendbuff + (size_t)r * bytes, bytes, r, false});
@@ -269,6 +283,8 @@ NCCL_EXPORT ncclResult_t ncclGather(const void* sendbuff, void* recvbuff, size_t
   INFO("Gather: opCount %lx sendbuff %p recvbuff %p count %zu datatype %d root %d comm %p [nranks=%d] stream %p",
        (unsigned long)comm->opCount, sendbuff, recvbuff, count, (int)datatype, root, (void*)comm, comm->nRanks, (void*)stream);
   const size_t bytes = count * (size_t)ts;
+  if (symA2AEligible(comm, sendbuff, bytes, count))
+    return symA2ASubmit({FUNC_SYM_GATHER, "Gather", sendbuff, recvbuff, count, datatype, ncclSum, root, comm, stream});
   std::vector<P2pOp> ops;
   ops.push_back({comm, stream, (void*)sendbuff, bytes, root, false});
   if (comm->rank == root)
