@@ -111,12 +111,17 @@ tests/native/xgmi_probe: tests/native/xgmi_probe.hip
 
 .PHONY: xgmi-probe
 
+# The host sources every CPU plan driver compiles (and their sanitizer twins under build/asan/), and the stubs the
+# drivers share
+PLANSRC  := $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc
+PLANDEPS := $(PLANSRC) $(wildcard tests/native/*.h) $(HDRS)
+PLANCXX  := $(CXX) -O1 -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude
+
 # CPU test driver of enqueue.cc's planning (no GPU: launches and the few HIP calls are stubbed)
 plan-test: tests/native/plan_test
 
-tests/native/plan_test: tests/native/plan_test.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
-	$(CXX) -O1 -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -o $@ tests/native/plan_test.cc \
-	  $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
+tests/native/plan_test: tests/native/plan_test.cc $(PLANDEPS)
+	$(PLANCXX) -o $@ tests/native/plan_test.cc $(PLANSRC) -lpthread
 
 .PHONY: plan-test
 
@@ -124,9 +129,8 @@ tests/native/plan_test: tests/native/plan_test.cc $(SRCDIR)/enqueue.cc $(SRCDIR)
 # llPartBounds, called from both sides); stubs like plan_test's
 bcast-plan-test: tests/native/bcast_plan_test
 
-tests/native/bcast_plan_test: tests/native/bcast_plan_test.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
-	$(CXX) -O1 -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -o $@ tests/native/bcast_plan_test.cc \
-	  $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
+tests/native/bcast_plan_test: tests/native/bcast_plan_test.cc $(PLANDEPS)
+	$(PLANCXX) -o $@ tests/native/bcast_plan_test.cc $(PLANSRC) -lpthread
 
 .PHONY: bcast-plan-test
 
@@ -142,9 +146,8 @@ tests/native/bcast_example: tests/native/bcast_example.cc include/nccl.h $(LIBDI
 # p2pSteps / sliceBounds, called from both sides); launches and the few HIP calls are stubbed
 p2p-plan-test: tests/native/p2p_plan_test
 
-tests/native/p2p_plan_test: tests/native/p2p_plan_test.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
-	$(CXX) -O1 -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -o $@ tests/native/p2p_plan_test.cc \
-	  $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
+tests/native/p2p_plan_test: tests/native/p2p_plan_test.cc $(SRCDIR)/p2p.cc $(PLANDEPS)
+	$(PLANCXX) -o $@ tests/native/p2p_plan_test.cc $(SRCDIR)/p2p.cc $(PLANSRC) -lpthread
 
 .PHONY: p2p-plan-test
 
@@ -152,9 +155,8 @@ tests/native/p2p_plan_test: tests/native/p2p_plan_test.cc $(SRCDIR)/p2p.cc $(SRC
 # launches and the few HIP calls are stubbed
 rma-plan-test: tests/native/rma_plan_test
 
-tests/native/rma_plan_test: tests/native/rma_plan_test.cc $(SRCDIR)/rma.cc $(SRCDIR)/group.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
-	$(CXX) -O1 -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -o $@ tests/native/rma_plan_test.cc \
-	  $(SRCDIR)/rma.cc $(SRCDIR)/group.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
+tests/native/rma_plan_test: tests/native/rma_plan_test.cc $(SRCDIR)/rma.cc $(SRCDIR)/group.cc $(SRCDIR)/p2p.cc $(PLANDEPS)
+	$(PLANCXX) -o $@ tests/native/rma_plan_test.cc $(SRCDIR)/rma.cc $(SRCDIR)/group.cc $(SRCDIR)/p2p.cc $(PLANSRC) -lpthread
 
 .PHONY: rma-plan-test
 
@@ -202,21 +204,21 @@ tests/native/export_check_test: tests/native/export_check_test.cc $(SRCDIR)/ipc.
 	$(CXX) -O1 -g -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -o $@ tests/native/export_check_test.cc \
 	  $(SRCDIR)/ipc.cc $(SRCDIR)/debug.cc -lpthread $(HIPRT)
 
-build/asan/bcast_plan_test: tests/native/bcast_plan_test.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
+build/asan/bcast_plan_test: tests/native/bcast_plan_test.cc $(PLANDEPS)
 	@mkdir -p $(dir $@)
-	$(SANCXX) $(ASAN) -o $@ tests/native/bcast_plan_test.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
+	$(SANCXX) $(ASAN) -o $@ tests/native/bcast_plan_test.cc $(PLANSRC) -lpthread
 
-build/asan/p2p_plan_test: tests/native/p2p_plan_test.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
+build/asan/p2p_plan_test: tests/native/p2p_plan_test.cc $(SRCDIR)/p2p.cc $(PLANDEPS)
 	@mkdir -p $(dir $@)
-	$(SANCXX) $(ASAN) -o $@ tests/native/p2p_plan_test.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
+	$(SANCXX) $(ASAN) -o $@ tests/native/p2p_plan_test.cc $(SRCDIR)/p2p.cc $(PLANSRC) -lpthread
 
-build/asan/rma_plan_test: tests/native/rma_plan_test.cc $(SRCDIR)/rma.cc $(SRCDIR)/group.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
+build/asan/rma_plan_test: tests/native/rma_plan_test.cc $(SRCDIR)/rma.cc $(SRCDIR)/group.cc $(SRCDIR)/p2p.cc $(PLANDEPS)
 	@mkdir -p $(dir $@)
-	$(SANCXX) $(ASAN) -o $@ tests/native/rma_plan_test.cc $(SRCDIR)/rma.cc $(SRCDIR)/group.cc $(SRCDIR)/p2p.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
+	$(SANCXX) $(ASAN) -o $@ tests/native/rma_plan_test.cc $(SRCDIR)/rma.cc $(SRCDIR)/group.cc $(SRCDIR)/p2p.cc $(PLANSRC) -lpthread
 
-build/asan/plan_test: tests/native/plan_test.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc $(HDRS)
+build/asan/plan_test: tests/native/plan_test.cc $(PLANDEPS)
 	@mkdir -p $(dir $@)
-	$(SANCXX) $(ASAN) -o $@ tests/native/plan_test.cc $(SRCDIR)/enqueue.cc $(SRCDIR)/debug.cc -lpthread
+	$(SANCXX) $(ASAN) -o $@ tests/native/plan_test.cc $(PLANSRC) -lpthread
 
 .PHONY: sanitize
 

@@ -1,5 +1,5 @@
 // bcast_plan_test.cc — CPU test driver of the Broadcast plan (enqueue.cc) and of the partition the Broadcast kernels
-// walk. Compiled with enqueue.cc and debug.cc like plan_test (no GPU: launches and the few HIP calls are stubbed), it
+// walk. Compiled with the planning sources like plan_test (no GPU: launches and the few HIP calls are stubbed, plan_stubs.h), it
 // slices every plan with the SAME host-callable functions the kernels call (device_abi.h blockLenOf / sliceBounds /
 // llPartBounds), so nothing of the arithmetic is restated here.
 //
@@ -18,68 +18,16 @@
 
 #include <vector>
 
-#include "../../nccl_amd/csrc/core.h"
-
-extern "C" {
-hipError_t hipSetDevice(int) { return hipSuccess; }
-hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
-hipError_t hipGetLastError(void) { return hipSuccess; }
-const char* hipGetErrorString(hipError_t) { return "stub"; }
-hipError_t hipPointerGetAttributes(hipPointerAttribute_t*, const void*) { return hipErrorInvalidValue; }
-hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
-hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned int) { return hipSuccess; }
-hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus* st) {
-  *st = hipStreamCaptureStatusNone;
-  return hipSuccess;
-}
-}
-
-namespace ncclamd {
-static LaunchPlan gPlan;
-static int gLaunches = 0;
-ncclResult_t launchPlan(const LaunchPlan& p) {
-  gPlan = p;
-  gLaunches++;
-  return ncclSuccess;
-}
-ncclResult_t launchSymPlan(const SymPlan&) { return ncclInternalError; }  // Broadcast never plans a zero-copy kernel
-ncclWindow_vidmem* findSymWindow(ncclComm*, const void*, size_t) { return nullptr; }
-bool regLookup(ncclComm*, hipStream_t, const void*, size_t, const void*, size_t, const char**, char**, bool) { return true; }
-bool groupActive() { return false; }
-ncclResult_t groupDeferColl(const CollInfo&) { return ncclSuccess; }
-void groupRecordError(ncclResult_t) {}
-void tunerPick(ncclComm*, CollFunc, size_t, int, int, int, int*, int* nch) { *nch = 0; }
-bool regCovers(ncclComm*, const void*, size_t) { return true; }  // "registered": the plan must stay staged anyway
-ncclResult_t commCheck(const ncclComm*, const char*, const char*) { return ncclSuccess; }
-void commPollAsync(ncclComm*) {}
-void ipcDrainReleases() {}
-void ipcProgressReleases() {}
-void regProgress(ncclComm*) {}
-void regRecordUse(ncclComm*, const SymPlan&) {}
-ncclResult_t bounceLaunch(ncclComm*, const SymPlan&) { return ncclInternalError; }
-void ipcNoteLaunch(hipStream_t, int) {}
-bool ipcLibraryIdle() { return true; }
-}  // namespace ncclamd
+#define PLAN_STUBS_NO_GROUP
+#include "plan_stubs.h"
 
 using namespace ncclamd;
 
+// Broadcast never plans a zero-copy kernel: a zero-copy launch is an error, and the buffers count as registered
+// (regLookup and regCovers answer true), so that a plan that stayed staged did so for being a Broadcast's
 static void initComm(ncclComm& comm, int n, size_t slotBytes) {
-  comm.startMagic = comm.endMagic = kCommMagic;
-  comm.rank = 0;
-  comm.nRanks = n;
-  comm.device = 0;
-  comm.minCTAs = 1;
-  comm.maxCTAs = comm.maxChannels = 256;
-  comm.nSlots = 2;
-  if (slotBytes == 0) {  // commDefaults' slot size, as plan_test
-    slotBytes = ((size_t)1 << 30) / (256 * 2 * 2 * (n > 1 ? n : 2));
-    if (slotBytes > ((size_t)1 << 20)) slotBytes = (size_t)1 << 20;
-    if (slotBytes < ((size_t)16 << 10)) slotBytes = (size_t)16 << 10;
-  }
-  comm.slotBytes = slotBytes;
-  comm.chanCap = 256;
-  comm.devComm = (DevComm*)0x1000;
-  loadTuning(&comm.tune);
+  gStubs.refuseSymLaunch = gStubs.regLookupAlways = gStubs.regCoversAnswer = true;
+  stubComm(comm, n, 0, slotBytes, 256);
   resolveLinkChannels(&comm.tune, n, getenv("NCCL_MAX_CTAS") != nullptr);
 }
 
@@ -97,11 +45,11 @@ static void initComm(ncclComm& comm, int n, size_t slotBytes) {
 static bool checkOne(int n, size_t bytes, size_t slotBytes, const char* proto, int* kind) {
   ncclComm comm;
   initComm(comm, n, slotBytes);
-  gLaunches = 0;
+  gStubs.launches = 0;
   const ncclResult_t r = ncclBroadcast((const void*)0x10000000ull, (void*)0x20000000ull, bytes, ncclUint8, (int)(bytes % n),
                                        &comm, nullptr);
-  REQUIRE(r == ncclSuccess && gLaunches == 1, "n %d bytes %zu proto %s: result %d, %d launches", n, bytes, proto, (int)r, gLaunches);
-  const LaunchPlan& p = gPlan;
+  REQUIRE(r == ncclSuccess && gStubs.launches == 1, "n %d bytes %zu proto %s: result %d, %d launches", n, bytes, proto, (int)r, gStubs.launches);
+  const LaunchPlan& p = gStubs.plan;
   REQUIRE(p.func == FUNC_BROADCAST && p.eltSize == 1, "n %d bytes %zu: func %d eltSize %d", n, bytes, (int)p.func, p.eltSize);
   if (p.algo == ALGO_LL) {
     const LLOp& o = p.ll.ops[0];
@@ -170,9 +118,9 @@ int main(int argc, char** argv) {
     ncclComm comm;
     initComm(comm, n, 0);
     const ncclResult_t r = ncclBroadcast((const void*)0x10000000ull, (void*)0x20000000ull, bytes, ncclUint8, root, &comm, nullptr);
-    printf("result=%d launches=%d\n", (int)r, gLaunches);
-    if (r != ncclSuccess || gLaunches == 0) return 0;
-    const LaunchPlan& p = gPlan;
+    printf("result=%d launches=%d\n", (int)r, gStubs.launches);
+    if (r != ncclSuccess || gStubs.launches == 0) return 0;
+    const LaunchPlan& p = gStubs.plan;
     if (p.algo == ALGO_LL)
       printf("algo=%s nch=%d part=%lu root=%d\n", p.ll.ops[0].proto == LLP_LL64 ? "ll128" : "ll", p.nChannels,
              (unsigned long)p.ll.ops[0].part, p.ll.ops[0].root);

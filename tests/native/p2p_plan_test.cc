@@ -20,26 +20,7 @@
 #include <map>
 #include <vector>
 
-#include "../../nccl_amd/csrc/core.h"
-
-extern "C" {
-hipError_t hipSetDevice(int) { return hipSuccess; }
-hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
-hipError_t hipGetLastError(void) { return hipSuccess; }
-const char* hipGetErrorString(hipError_t) { return "stub"; }
-hipError_t hipPointerGetAttributes(hipPointerAttribute_t*, const void*) { return hipErrorInvalidValue; }
-hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
-hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned int) { return hipSuccess; }
-hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus* st) {
-  *st = hipStreamCaptureStatusNone;
-  return hipSuccess;
-}
-static int gCopies = 0;
-hipError_t hipMemcpyAsync(void*, const void*, size_t, hipMemcpyKind, hipStream_t) {
-  gCopies++;
-  return hipSuccess;
-}
-}
+#include "plan_stubs.h"
 
 namespace ncclamd {
 static int gLaunches = 0;
@@ -47,21 +28,6 @@ ncclResult_t launchP2pKernel(const ncclComm*, const P2pLaunch&, hipStream_t) {
   gLaunches++;
   return ncclSuccess;
 }
-ncclResult_t launchPlan(const LaunchPlan&) { return ncclInternalError; }
-ncclResult_t launchSymPlan(const SymPlan&) { return ncclInternalError; }
-ncclWindow_vidmem* findSymWindow(ncclComm*, const void*, size_t) { return nullptr; }
-bool regLookup(ncclComm*, hipStream_t, const void*, size_t, const void*, size_t, const char**, char**, bool) { return true; }
-void tunerPick(ncclComm*, CollFunc, size_t, int, int, int, int*, int* nch) { *nch = 0; }
-bool regCovers(ncclComm*, const void*, size_t) { return true; }
-ncclResult_t commCheck(const ncclComm* c, const char*, const char*) { return c ? ncclSuccess : ncclInvalidArgument; }
-void commPollAsync(ncclComm*) {}
-void ipcDrainReleases() {}
-void ipcProgressReleases() {}
-void regProgress(ncclComm*) {}
-void regRecordUse(ncclComm*, const SymPlan&) {}
-ncclResult_t bounceLaunch(ncclComm*, const SymPlan&) { return ncclInternalError; }
-void ipcNoteLaunch(hipStream_t, int) {}
-bool ipcLibraryIdle() { return true; }
 // the group machinery, reduced to what an ungrouped p2p call needs: record, then plan and launch at the end
 static int gDepth = 0;
 static ncclResult_t gGroupError = ncclSuccess;
@@ -86,23 +52,10 @@ ncclResult_t groupEndInternal(ncclSimInfo_t*) {
 
 using namespace ncclamd;
 
+// p2p.cc launches no collective (a collective launch is an error); buffers count as registered
 static void initComm(ncclComm& comm, int n, int rank, size_t slotBytes, int chanCap) {
-  comm.startMagic = comm.endMagic = kCommMagic;
-  comm.rank = rank;
-  comm.nRanks = n;
-  comm.device = 0;
-  comm.minCTAs = 1;
-  comm.maxCTAs = comm.maxChannels = 256;
-  comm.nSlots = 2;
-  if (slotBytes == 0) {  // commDefaults' slot size, as plan_test
-    slotBytes = ((size_t)1 << 30) / (256 * 2 * 2 * (n > 1 ? n : 2));
-    if (slotBytes > ((size_t)1 << 20)) slotBytes = (size_t)1 << 20;
-    if (slotBytes < ((size_t)16 << 10)) slotBytes = (size_t)16 << 10;
-  }
-  comm.slotBytes = slotBytes;
-  comm.chanCap = chanCap;
-  comm.devComm = (DevComm*)0x1000;
-  loadTuning(&comm.tune);
+  gStubs.refuseLaunch = gStubs.refuseSymLaunch = gStubs.regLookupAlways = gStubs.regCoversAnswer = true;
+  stubComm(comm, n, rank, slotBytes, chanCap);
 }
 
 #define REQUIRE(cond, ...)          \

@@ -12,24 +12,7 @@
 #include <map>
 #include <vector>
 
-#include "../../nccl_amd/csrc/core.h"
-
-extern "C" {
-hipError_t hipSetDevice(int) { return hipSuccess; }
-hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
-hipError_t hipGetLastError(void) { return hipSuccess; }
-const char* hipGetErrorString(hipError_t) { return "stub"; }
-hipError_t hipPointerGetAttributes(hipPointerAttribute_t*, const void*) { return hipErrorInvalidValue; }
-hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = nullptr; return hipSuccess; }
-hipError_t hipEventDestroy(hipEvent_t) { return hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
-hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned int) { return hipSuccess; }
-hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus* st) {
-  *st = hipStreamCaptureStatusNone;
-  return hipSuccess;
-}
-hipError_t hipMemcpyAsync(void*, const void*, size_t, hipMemcpyKind, hipStream_t) { return hipSuccess; }
-}
+#include "plan_stubs.h"
 
 namespace ncclamd {
 struct Recorded {  // one launch, in launch order
@@ -48,29 +31,7 @@ ncclResult_t launchRmaWaitKernel(const ncclComm*, const RmaWaitArgs& w, hipStrea
   return ncclSuccess;
 }
 ncclResult_t launchP2pKernel(const ncclComm*, const P2pLaunch&, hipStream_t) { return ncclInternalError; }
-ncclResult_t launchPlan(const LaunchPlan&) { return ncclInternalError; }
-ncclResult_t launchSymPlan(const SymPlan&) { return ncclInternalError; }
-ncclWindow_vidmem* findSymWindow(ncclComm* comm, const void* p, size_t bytes) {  // register.cc's, over the test's windows
-  const uintptr_t a = (uintptr_t)p;
-  for (ncclWindow_vidmem* w : comm->windows) {
-    const uintptr_t b = (uintptr_t)w->userPtr;
-    if ((w->flags & NCCL_WIN_COLL_SYMMETRIC) && a >= b && a + bytes <= b + w->size) return w;
-  }
-  return nullptr;
-}
-bool regLookup(ncclComm*, hipStream_t, const void*, size_t, const void*, size_t, const char**, char**, bool) { return true; }
-void tunerPick(ncclComm*, CollFunc, size_t, int, int, int, int*, int* nch) { *nch = 0; }
 ModelCost modelCost(ModelAlgo, CollFunc, int, size_t bytes) { return {1.0, (double)bytes * 1e-4}; }
-bool regCovers(ncclComm*, const void*, size_t) { return true; }
-ncclResult_t commCheck(const ncclComm* c, const char*, const char*) { return c ? ncclSuccess : ncclInvalidArgument; }
-void commPollAsync(ncclComm*) {}
-void ipcDrainReleases() {}
-void ipcProgressReleases() {}
-void regProgress(ncclComm*) {}
-void regRecordUse(ncclComm*, const SymPlan&) {}
-ncclResult_t bounceLaunch(ncclComm*, const SymPlan&) { return ncclInternalError; }
-void ipcNoteLaunch(hipStream_t, int) {}
-bool ipcLibraryIdle() { return true; }
 thread_local bool tPlanOnly = false;
 }  // namespace ncclamd
 
@@ -83,17 +44,9 @@ struct Fixture {
   ncclComm comm;
   ncclWindow_vidmem src, dst;
   Fixture(int n, int rank, int chanCap) {
-    comm.startMagic = comm.endMagic = kCommMagic;
-    comm.rank = rank;
-    comm.nRanks = n;
-    comm.device = 0;
-    comm.minCTAs = 1;
-    comm.maxCTAs = comm.maxChannels = 256;
-    comm.nSlots = 2;
-    comm.slotBytes = 1 << 20;
-    comm.chanCap = chanCap;
-    comm.devComm = (DevComm*)0x1000;
-    loadTuning(&comm.tune);
+    // rma.cc launches no collective (a collective launch is an error); buffers count as registered
+    gStubs.refuseLaunch = gStubs.refuseSymLaunch = gStubs.regLookupAlways = gStubs.regCoversAnswer = true;
+    stubComm(comm, n, rank, 1 << 20, chanCap);
     memset(&src, 0, sizeof(src));
     memset(&dst, 0, sizeof(dst));
     src.comm = dst.comm = &comm;
