@@ -201,6 +201,115 @@ def nan_cap_ok(want: np.ndarray, dtype: int) -> bool:
     return bool(np.isnan(oracle.to_f32(dtype, want)).mean() <= 0.10)
 
 
+# storage bits, explicit mantissa bits M and exponent bias of the float types edge_inputs builds
+_EDGE_FORMAT = {6: (16, 10, 15), 9: (16, 7, 127), 7: (32, 23, 127), 8: (64, 52, 1023)}
+EDGE_BLOCKS = 18
+
+
+def _edge_base(dtype: int) -> np.ndarray:
+    """The base list of edge_inputs as storage bits: every fp16 / bf16 pattern; for fp32 / fp64 every sign x every
+    exponent field x 16 / 8 mantissas at the edges of the field (all zeros, all ones, around the half, the 0x55...
+    patterns, the middle bit)."""
+    bits, M, _ = _EDGE_FORMAT[dtype]
+    ut = np.dtype(f"u{bits // 8}")
+    if bits == 16:
+        return np.arange(65536, dtype=ut)
+    ones = (1 << M) - 1
+    half = 1 << (M - 1)
+    mant = [0, 1, 2, ones, ones - 1, half, half - 1, half + 1, ones // 3, 2 * (ones // 3), 1 << (M // 2), ones >> 1,
+            3 << (M - 2), 5, ones ^ 5, half | ((ones // 3) >> 1)]
+    mant = np.array(mant[:16 if dtype == 7 else 8], dtype=ut)
+    sign = np.array([0, 1], dtype=ut) << ut.type(bits - 1)
+    expo = np.arange(1 << (bits - 1 - M), dtype=ut) << ut.type(M)
+    return (sign[:, None, None] | expo[None, :, None] | mant[None, None, :]).reshape(-1)
+
+
+_edge_cache: dict = {}
+
+
+def edge_inputs(dtype: int, n: int):
+    """Inputs of n = 2 or 3 ranks (storage arrays of fp16 6, bf16 9, fp32 7 or fp64 8, read-only and shared between
+    callers) that pair every value of the base list `a` (_edge_base) with 18 partners chosen for what goes wrong in a
+    rounding: rank 0 holds `a` 18 times, rank 1 the 18 blocks
+      1 a permutation of a            2 a itself (doubling, squaring: overflow and underflow)
+      3 -a (exact cancellation, +-0 meeting in Min / Max)            4 the ulp neighbour (the bits + 1, wrapped)
+      5 minus the ulp neighbour (tiny and subnormal exact results)
+      6 exactly half an ulp of a, same sign (every Sum a rounding tie)   7 block 6 | 1 (just above the tie)
+      8 block 6 negated (the tie from below)
+      9 a byte-swapped (16-bit) / reversed (fp32, fp64): large exponents against small ones
+      10-18 the constants 1, +-max finite, min subnormal, min normal, -0, +Inf, 1 + 1 ulp and 0.3333... x 2^-1
+    and rank 2 holds rank 0's elements at (j * 25173 + 13849) mod length. Signalling NaNs are quieted in every array
+    (their handling is the hardware's, tests/test_numerics.py)."""
+    if (dtype, n) in _edge_cache:
+        return _edge_cache[(dtype, n)]
+    assert n in (2, 3)
+    bits, M, bias = _EDGE_FORMAT[dtype]
+    ut = np.dtype(f"u{bits // 8}")
+    U = ut.type
+    ones = (1 << M) - 1
+    sign = U(1 << (bits - 1))
+    emax = (1 << (bits - 1 - M)) - 1
+    a = _edge_base(dtype)
+    ln = a.size
+    s = a & sign
+    e = ((a & ~sign) >> U(M)).astype(np.int64)
+    # half an ulp of a: a normal number while a's exponent field is at least M + 2, a subnormal power of two below
+    # that, the smallest subnormal (the nearest there is) for the two lowest fields
+    half = np.where(e >= M + 2, np.maximum(e - (M + 1), 0) << M,
+                    np.where(e >= 2, np.int64(1) << np.clip(e - 2, 0, M), 1)).astype(ut) | s
+    swapped = a.byteswap() if bits == 16 else a[::-1]
+    consts = [bias << M, ((emax - 1) << M) | ones, (1 << (bits - 1)) | ((emax - 1) << M) | ones, 1, 1 << M,
+              1 << (bits - 1), emax << M, (bias << M) + 1, ((bias - 2) << M) | (ones // 3)]
+    blocks = [a[(np.arange(ln, dtype=np.int64) * 40503) % ln], a, a ^ sign, a + U(1), (a + U(1)) ^ sign, half,
+              half | U(1), half ^ sign, swapped] + [np.full(ln, c, dtype=ut) for c in consts]
+    assert len(blocks) == EDGE_BLOCKS
+    r0 = np.tile(a, EDGE_BLOCKS)
+    ranks = [r0, np.concatenate(blocks)]
+    if n == 3:
+        ranks.append(r0[(np.arange(r0.size, dtype=np.int64) * 25173 + 13849) % r0.size])
+    qbit, expm = U(1 << (M - 1)), U(emax << M)
+    out = []
+    for x in ranks:
+        x = np.ascontiguousarray(x, dtype=ut).copy()
+        snan = ((x & expm) == expm) & ((x & U(ones)) != 0) & ((x & qbit) == 0)
+        x[snan] |= qbit
+        x = x.view(oracle.NP_STORAGE[dtype])
+        x.setflags(write=False)
+        out.append(x)
+    _edge_cache[(dtype, n)] = out
+    return out
+
+
+def defined_mask(ins, dtype: int, op: int) -> np.ndarray:
+    """The elements of a built-in operator's result over float inputs `ins` whose NaN bits are compared with the
+    oracle's as well (same_bits compares NaN by position only): for Sum / Prod / Avg those where exactly one NaN
+    arises in the fold (one NaN input, none made from Inf - Inf / 0 x Inf: the rule of test_gpu_collectives.py
+    _comparable and _single_nan_errors); Min / Max (explicit selects): every element."""
+    from tests.test_gpu_collectives import _comparable
+    keep = _comparable(ins, dtype, op)
+    if op in (2, 3):
+        return keep
+    return keep & (np.isnan(np.stack([oracle.to_f32(dtype, x) for x in ins])).sum(0) == 1)
+
+
+def edge_errors(got: np.ndarray, want: np.ndarray, one: np.ndarray, dtype: int, what: str):
+    """Error strings of one result against the oracle's: same_bits over every element, and the elements of `one`
+    (defined_mask) bit for bit."""
+    errs = []
+    g, w = _raw(got), _raw(want)
+    if not same_bits(got, want, dtype):
+        nan = np.isnan(oracle.to_f32(dtype, want))
+        bad = np.nonzero((g != w) & ~(nan & np.isnan(oracle.to_f32(dtype, got))))[0]
+        errs.append(f"{what}: {bad.size} of {w.size} elements differ, first at {bad[:5].tolist()} got "
+                    f"{[hex(int(v)) for v in g[bad[:3]]]} want {[hex(int(v)) for v in w[bad[:3]]]}")
+    if not np.array_equal(g[one], w[one]):
+        bad = np.nonzero((g != w) & one)[0]
+        errs.append(f"{what}: {bad.size} of {int(one.sum())} elements with a defined NaN differ, first at "
+                    f"{bad[:5].tolist()} got {[hex(int(v)) for v in g[bad[:3]]]} want "
+                    f"{[hex(int(v)) for v in w[bad[:3]]]}")
+    return errs
+
+
 def out_count(coll: str, n: int, count: int) -> int:
     return {"allreduce": count, "reducescatter": count // n, "allgather": count * n, "reduce": count}[coll]
 

@@ -52,8 +52,25 @@ uint64_t nx_red(int dt, int op, uint64_t arg, uint64_t a, uint64_t b) { return d
 uint64_t nx_pre(int dt, int op, uint64_t arg, uint64_t a) { return dispatch(dt, op, arg, a, 0, 1); }
 uint64_t nx_post(int dt, int op, uint64_t arg, uint64_t a) { return dispatch(dt, op, arg, a, 0, 2); }
 // pre(x) for n elements of dtype's storage width (one call per array: the exhaustive pre-op checks)
+static int typeSize(int dt) { return dt <= 1 || dt >= 10 ? 1 : dt == 6 || dt == 9 ? 2 : dt == 2 || dt == 3 || dt == 7 ? 4 : 8; }
+// the whole fold of n sources in the kernels' operand order, for count elements of dtype's storage width:
+// acc = pre(src0); acc = red(pre(src_k), acc) for k = 1 .. n-1; out = post(acc) (one call per array)
+extern "C" void nx_fold_array(int dt, int op, uint64_t arg, const void* const* srcs, int n, void* out, uint64_t count) {
+  const int ts = typeSize(dt);
+  for (uint64_t i = 0; i < count; i++) {
+    uint64_t acc = 0;
+    for (int k = 0; k < n; k++) {
+      uint64_t x = 0;
+      __builtin_memcpy(&x, (const char*)srcs[k] + i * ts, ts);
+      x = dispatch(dt, op, arg, x, 0, 1);
+      acc = k == 0 ? x : dispatch(dt, op, arg, x, acc, 0);
+    }
+    acc = dispatch(dt, op, arg, acc, 0, 2);
+    __builtin_memcpy((char*)out + i * ts, &acc, ts);
+  }
+}
 extern "C" void nx_pre_array(int dt, int op, uint64_t arg, const void* in, void* out, uint64_t n) {
-  const int ts = dt <= 1 || dt >= 10 ? 1 : dt == 6 || dt == 9 ? 2 : dt == 2 || dt == 3 || dt == 7 ? 4 : 8;
+  const int ts = typeSize(dt);
   for (uint64_t i = 0; i < n; i++) {
     uint64_t x = 0;
     __builtin_memcpy(&x, (const char*)in + i * ts, ts);

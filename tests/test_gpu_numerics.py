@@ -4,7 +4,8 @@
   f32ToFp8SatHw: v_cvt_f32_fp8 / v_cvt_pk_fp8_f32 with a satfinite clamp and software NaN) equal the software
   conversions (checked against the oracle on the host, tests/test_numerics.py) for every code and every half;
 * every (a, b) byte pair of e4m3 / e5m2 / uint8 / int8 through an n=2 AllReduce (both ranks on the one GPU)
-  for every operator, on the LL kernel and on the staged kernel, bit-exact vs the oracle — the reference's
+  for every operator, on the LL kernel and on the staged kernel (there also ReduceScatter and Reduce) and on the
+  forced LL128, one-shot, registered zero-copy, ring and chain kernels, bit-exact vs the oracle — the reference's
   fp8 functors (src/device/reduce_kernel.h:461-487) and integer functors (:330-357, :936-966)."""
 import json
 import os
@@ -44,8 +45,38 @@ def _pairs(dtype):
     return [a.view(npdt), b.view(npdt)]
 
 
-@pytest.mark.parametrize("proto", ["LL", "^LL"])
+ONE_BYTE_TYPES = (10, 11, 1, 0)
+FORCED_PATHS = ("LL128", "ONESHOT", "REGISTERED", "RING", "TREE")
+
+
+def _job_one_byte_pairs(path):
+    """Every byte pair of the four 1-byte types through a forced path's AllReduce at n = 2 for every operator (a
+    spawned worker whose environment forces the path, tests/test_gpu_edge_values.py run_set: slices every forced path
+    takes, guarded buffers, the oracle's fold for the path)."""
+    from tests.test_gpu_edge_values import comms_under, destroy, run_set, slice_elems
+    cs = comms_under(2)
+    errs = []
+    for dtype in ONE_BYTE_TYPES:
+        errs += run_set(cs, "allreduce", dtype, _pairs(dtype), slice_elems(dtype), path == "REGISTERED", path)
+    destroy(cs)
+    return errs
+
+
+@pytest.mark.parametrize("proto", ["LL", "^LL", *FORCED_PATHS])
 def test_one_byte_every_pair(built, proto, monkeypatch):
+    """Every (a, b) byte pair of e4m3 / e5m2 / uint8 / int8, every operator, n = 2. LL and ^LL (the LL kernel and the
+    staged kernel, chosen by NCCL_PROTO): AllReduce, ReduceScatter and Reduce to root 1. The other paths — LL128,
+    one-shot, the zero-copy kernel on registered buffers, the reference's ring and chain — are forced in a spawned
+    worker whose kernel log must name the path's kernel for every element type and operator (integer Avg is
+    SumPostDiv, template argument 4; fp8 Avg PreMulSum, 3) and no other kernel of those types."""
+    if proto in FORCED_PATHS:
+        from tests.test_gpu_edge_values import check_kernel_log
+        from tests.test_gpu_premulsum import PATHS, spawn
+        (errs, klog, _), = spawn([(_job_one_byte_pairs, proto, PATHS[proto][0])], timeout=150)
+        assert not errs, "\n".join(errs[:10])
+        for dtype in ONE_BYTE_TYPES:
+            check_kernel_log(klog, proto, dtype, (0, 1, 2, 3) if dtype >= 10 else (0, 1, 2, 4), extra=())
+        return
     import torch
     import nccl_amd
     from tests import gpu_cases as G
@@ -60,6 +91,8 @@ def test_one_byte_every_pair(built, proto, monkeypatch):
             ins = _pairs(dtype)
             for op in (0, 1, 2, 3, 4):  # sum, prod, max, min, avg
                 errs += G.run_case(cs, "allreduce", dtype, op, ins[0].size, 0, seed=0, inputs=ins)
+                errs += G.run_case(cs, "reducescatter", dtype, op, ins[0].size, 0, seed=0, inputs=ins)
+                errs += G.run_case(cs, "reduce", dtype, op, ins[0].size, 0, seed=0, inputs=ins, root=1)
     finally:
         for c in comms:
             c.destroy()

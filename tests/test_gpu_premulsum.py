@@ -32,19 +32,20 @@ KERNEL_TYPE = {0: "unsigned char", 1: "unsigned char", 2: "unsigned int", 3: "un
                10: "ncclamd::e4m3_t", 11: "ncclamd::e5m2_t"}
 
 _REF = {"NCCL_BUFFSIZE": "16384", "NCCL_MAX_CTAS": "5"}
-# path -> (communicator environment, the AllReduce kernel the log must name with operator template argument 3)
+# path -> (communicator environment, the AllReduce kernel the log must name: {T} the element type, {OP} the operator
+# template argument — 3, DEV_PREMULSUM, for every case of this file; path_pattern)
 PATHS = {
-    "LL": ({"NCCL_PROTO": "LL"}, r"llKernel<{T}, 3, \d+, 0>"),
-    "LL128": ({"NCCL_PROTO": "LL128"}, r"llKernel<{T}, 3, \d+, 1>"),
-    "ONESHOT": ({"NCCL_ALGO": "ONESHOT"}, r"collKernel<{T}, 3, 4>"),
+    "LL": ({"NCCL_PROTO": "LL"}, r"llKernel<{T}, {OP}, \d+, 0>"),
+    "LL128": ({"NCCL_PROTO": "LL128"}, r"llKernel<{T}, {OP}, \d+, 1>"),
+    "ONESHOT": ({"NCCL_ALGO": "ONESHOT"}, r"collKernel<{T}, {OP}, 4>"),
     "DIRECT": ({"NCCL_ALGO": "DIRECT", "NCCL_PROTO": "Simple", "NCCL_AMD_SLOT_BYTES": "4096", "NCCL_AMD_NSLOTS": "2",
-                "NCCL_MAX_CTAS": "7"}, r"collKernel<{T}, 3, 0>"),
+                "NCCL_MAX_CTAS": "7"}, r"collKernel<{T}, {OP}, 0>"),
     "DIRECT_PULLS": ({"NCCL_ALGO": "DIRECT", "NCCL_PROTO": "Simple", "NCCL_AMD_AG_PULL": "1", "NCCL_AMD_RS_PULL": "1"},
-                     r"collKernel<{T}, 3, 0>"),
-    "REGISTERED": ({"NCCL_PROTO": "Simple"}, r"symKernel<{T}, 3, [01]>"),
-    "RING": (dict(_REF, NCCL_ALGO="RING"), r"pipeKernel<{T}, 3, 0>"),
-    "TREE": (dict(_REF, NCCL_ALGO="TREE"), r"pipeKernel<{T}, 3, 3>"),
-    "REF_ORDER": (dict(_REF, NCCL_AMD_REF_ORDER="1"), r"collKernel<{T}, 3, 5>"),
+                     r"collKernel<{T}, {OP}, 0>"),
+    "REGISTERED": ({"NCCL_PROTO": "Simple"}, r"symKernel<{T}, {OP}, [01]>"),
+    "RING": (dict(_REF, NCCL_ALGO="RING"), r"pipeKernel<{T}, {OP}, 0>"),
+    "TREE": (dict(_REF, NCCL_ALGO="TREE"), r"pipeKernel<{T}, {OP}, 3>"),
+    "REF_ORDER": (dict(_REF, NCCL_AMD_REF_ORDER="1"), r"collKernel<{T}, {OP}, 5>"),
 }
 FULL_LIST_PATHS = ("LL", "DIRECT")   # the whole scalar list for every type runs on these two
 DIRECT_SIMPLE = {"NCCL_ALGO": "DIRECT", "NCCL_PROTO": "Simple"}
@@ -295,7 +296,7 @@ def _worker_main(job, arg, env, q):
             os.environ["NCCL_DEBUG_FILE"] = dlog
         import torch
         torch.cuda.set_device(0)
-        errs = JOBS[job](arg)
+        errs = (job if callable(job) else JOBS[job])(arg)   # (another test file passes a function of its own)
         torch.cuda.synchronize()
         out = (errs, open(klog).read().splitlines() if os.path.exists(klog) else [],
                open(dlog).read() if os.path.exists(dlog) else "")
@@ -308,9 +309,10 @@ def _worker_main(job, arg, env, q):
         q.put(([f"exception {e!r}\n{traceback.format_exc()}"], [], ""))
 
 
-def spawn(jobs):
+def spawn(jobs, timeout=240):
     """Run [(job, arg, env), ...] each in a fresh child process, all at once (at most four); returns their
-    (errors, kernel log lines, debug log) in order."""
+    (errors, kernel log lines, debug log) in order. A worker that has not reported after `timeout` seconds is killed
+    and fails the test."""
     _torch()
     assert len(jobs) <= 4
     ctx = mp.get_context("spawn")
@@ -322,7 +324,7 @@ def spawn(jobs):
     try:
         for (job, arg, _), q in zip(jobs, qs):
             try:
-                outs.append(q.get(timeout=240))
+                outs.append(q.get(timeout=timeout))
             except queue.Empty:
                 raise AssertionError(f"worker {job} {arg} did not report")
     finally:
@@ -334,12 +336,18 @@ def spawn(jobs):
     return outs
 
 
+def path_pattern(pattern, T, op):
+    """A kernel name pattern ({T}, {OP}) compiled for the element type T and the operator template argument `op` (a
+    number, or a regular expression such as "[0-3]")."""
+    return re.compile(pattern.replace("{OP}", str(op)).replace("{T}", re.escape(T)))
+
+
 def kernels_with_op3(klog, pattern, dtypes=ALL_TYPES):
-    """For every datatype's kernel element type, the log line matching `pattern` (an AssertionError names the
-    element types whose kernel never ran); returns the matched kernel names."""
+    """For every datatype's kernel element type, the log line matching `pattern` with operator template argument 3
+    (an AssertionError names the element types whose kernel never ran); returns the matched kernel names."""
     names, missing = [], []
     for T in sorted({KERNEL_TYPE[d] for d in dtypes}):
-        rx = re.compile(pattern.replace("{T}", re.escape(T)))
+        rx = path_pattern(pattern, T, 3)
         hit = [m.group(0) for ln in klog for m in [rx.search(ln)] if m]
         if hit:
             names.append(hit[0])

@@ -243,3 +243,99 @@ def test_premul_pre_integers(nx, dtype, bits):
         want = oracle.all_reduce([x], dtype, premul_scalar_bits=s)
         assert np.array_equal(got, want), (dtype, hex(s))
         assert [int(v) for v in got.view(ut)] == [(int(v) * s) & ones for v in x.view(ut)], (dtype, hex(s))
+
+
+# ---- the built-in operators over the edge-value pairs (tests/gpu_cases.py edge_inputs): the host branch of the
+# functors the GPU file tests/test_gpu_edge_values.py runs on the device ----
+
+def _nx_fold(nx, dtype, devop, arg, srcs):
+    """nx_fold_array: acc = pre(src0); acc = red(pre(src_k), acc); post(acc), one call for the whole arrays."""
+    nx.nx_fold_array.restype = None
+    nx.nx_fold_array.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p),
+                                 ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64]
+    srcs = [np.ascontiguousarray(x) for x in srcs]
+    ptrs = (ctypes.c_void_p * len(srcs))(*[x.ctypes.data for x in srcs])
+    out = np.empty_like(srcs[0])
+    nx.nx_fold_array(dtype, devop, arg, ptrs, len(srcs), out.ctypes.data, out.size)
+    return out
+
+
+def _fold_vs_oracle(nx, dtype, op, ins):
+    """The host functors' fold of `ins` in rank order against oracle.reduce to the last rank — nccl_oracle.c
+    fold_elem from first = (root + 1) % n = 0: acc = pre(x0), then acc = f(pre(x_k), acc) for k = 1 .. n-1 — with the
+    GPU tests' comparison: every bit, NaN by position under the 10 % cap, the defined NaNs bit for bit."""
+    from tests import gpu_cases as G
+    n = len(ins)
+    devop, arg = oracle.dev_op(op, dtype, n)
+    want = oracle.reduce(ins, dtype, op, n - 1)
+    assert G.nan_cap_ok(want, dtype), f"dtype {dtype} op {op} n {n}: more than 10 % of the oracle's result is NaN"
+    got = _nx_fold(nx, dtype, devop, arg, ins)
+    errs = G.edge_errors(got, want, G.defined_mask(ins, dtype, op), dtype, f"dtype {dtype} op {op} n {n}")
+    if errs:
+        bad = np.nonzero(G._raw(got) != G._raw(want))[0][:3]
+        errs.append(f"inputs there: {[[hex(int(G._raw(x)[i])) for x in ins] for i in bad]}")
+    assert not errs, "\n".join(errs)
+
+
+def test_fold_array_entry_matches_scalar_entries(nx):
+    """The array entry point used below is nx_pre / nx_red / nx_post per element, in the order it documents."""
+    rng = np.random.default_rng(3)
+    srcs = [rng.integers(0, 65536, 500).astype(np.uint16) & 0x7BFF for _ in range(3)]
+    for dtype, devop, arg in ((6, 3, 0x3555), (9, 1, 0), (6, 2, 1)):
+        want = []
+        for x0, x1, x2 in zip(*srcs):
+            acc = nx.nx_pre(dtype, devop, arg, int(x0))
+            for x in (x1, x2):
+                acc = nx.nx_red(dtype, devop, arg, nx.nx_pre(dtype, devop, arg, int(x)), acc)
+            want.append(nx.nx_post(dtype, devop, arg, acc))
+        assert [int(v) for v in _nx_fold(nx, dtype, devop, arg, srcs)] == want, (dtype, devop)
+
+
+def test_edge_inputs_construction():
+    """edge_inputs: the base list sizes times 18 blocks, no signalling NaN, and on fp16 the half-ulp partner (block 6:
+    half the distance from a to its neighbour away from zero, a's sign) and the nine constants by value."""
+    from tests import gpu_cases as G
+    for dtype, size in ((6, 65536), (9, 65536), (7, 8192), (8, 32768)):
+        r0, r1, r2 = G.edge_inputs(dtype, 3)
+        assert r0.size == r1.size == r2.size == 18 * size and G._edge_base(dtype).size == size
+        assert all(np.array_equal(G._raw(x), G._raw(y)) for x, y in zip(G.edge_inputs(dtype, 2), (r0, r1)))
+        bits, M, _ = G._EDGE_FORMAT[dtype]
+        ut = np.dtype(f"u{bits // 8}").type
+        expm = ut(((1 << (bits - 1 - M)) - 1) << M)
+        for u in map(G._raw, (r0, r1, r2)):
+            assert not (((u & expm) == expm) & ((u & ut((1 << M) - 1)) != 0) & ((u & ut(1 << (M - 1))) == 0)).any()
+    r0, r1 = (G._raw(x) for x in G.edge_inputs(6, 2))
+    a, h = r0[5 * 65536:6 * 65536], r1[5 * 65536:6 * 65536]
+    e = (a >> 10) & 0x1F
+    finite = (e >= 2) & (e <= 29)    # half an ulp is a value of the type, the neighbour away from zero is finite
+    fa, fh = (x.view(np.float16).astype(np.float64) for x in (a, h))
+    up = (a + np.uint16(1)).view(np.float16).astype(np.float64)
+    assert np.array_equal(fh[finite] * 2, up[finite] - fa[finite])
+    c = [float(r1[(9 + k) * 65536:(9 + k) * 65536 + 1].view(np.float16)[0]) for k in range(9)]
+    assert c[:5] == [1.0, 65504.0, -65504.0, 2.0 ** -24, 2.0 ** -14] and c[5] == 0 and np.signbit(c[5])
+    assert c[6:8] == [np.inf, 1.0 + 2.0 ** -10] and abs(c[8] - 1.0 / 3.0) < 2.0 ** -12
+
+
+@pytest.mark.parametrize("n", [2, 3])
+@pytest.mark.parametrize("op", [0, 1, 2, 3, 4], ids=["sum", "prod", "max", "min", "avg"])
+@pytest.mark.parametrize("dtype", [6, 9, 7, 8], ids=["fp16", "bf16", "fp32", "fp64"])
+def test_edge_pairs_fold_matches_oracle(nx, dtype, op, n):
+    """Every base value against its 18 partners (ties, overflow, cancellation, subnormal results, signed zeros, every
+    fp16 / bf16 NaN) through the host functors, n = 2 (one hop) and n = 3 (two hops with a rounded intermediate, Avg's
+    inexact 1/3), every built-in operator (float Avg is PreMulSum by the type's 1/n)."""
+    from tests import gpu_cases as G
+    _fold_vs_oracle(nx, dtype, op, G.edge_inputs(dtype, n))
+
+
+@pytest.mark.parametrize("op", [2, 4], ids=["max", "avg"])
+@pytest.mark.parametrize("dtype", [10, 11], ids=["e4m3", "e5m2"])
+def test_fp8_every_pair_max_avg(nx, dtype, op):
+    """Every fp8 code pair under Max and Avg (test_small_float_reduce_matches_oracle runs Sum, Prod and Min)."""
+    a = np.repeat(np.arange(256, dtype=np.uint8), 256)
+    b = np.tile(np.arange(256, dtype=np.uint8), 256)
+    devop, arg = oracle.dev_op(op, dtype, 2)
+    want = oracle.reduce([a, b], dtype, op, 1)
+    got = _nx_fold(nx, dtype, devop, arg, [a, b])
+    fa, fb = oracle.to_f32(dtype, got), oracle.to_f32(dtype, want)
+    ok = (got == want) | (np.isnan(fa) & np.isnan(fb))
+    assert ok.all(), f"{(~ok).sum()} mismatches, e.g. a={a[~ok][:3]} b={b[~ok][:3]} got={got[~ok][:3]} want={want[~ok][:3]}"
