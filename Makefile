@@ -24,7 +24,7 @@ HDRS     := $(wildcard $(SRCDIR)/*.h) include/nccl.h
 
 all: lib oracle numerics-host bootstrap-test tuner-test nccl-perf comm-examples plan-test mapcheck-test xgmi-probe atomicity-probe \
      fp8-probe release-probe reuse-probe export-check-test barrier-probe bcast-plan-test bcast-example p2p-plan-test sendrecv-example \
-     rma-plan-test sym-a2a-plan-test
+     rma-plan-test sym-a2a-plan-test comm-split-test
 
 .PHONY: export-check-test
 export-check-test: tests/native/export_check_test
@@ -178,6 +178,17 @@ tests/native/sendrecv_example: tests/native/sendrecv_example.cc include/nccl.h $
 
 .PHONY: sendrecv-example
 
+# CPU test of ncclCommSplit / ncclCommShrink below the GPU: membership and inherited occupancy (split.h), the channel
+# cap they feed (enqueue.cc, its launches stubbed) and the subset rounds and rendezvous of the bootstrap, ranks as threads
+SPLITSRC := tests/native/comm_split_test.cc $(SRCDIR)/bootstrap.cc $(PLANSRC)
+comm-split-test: build/comm_split_test
+
+build/comm_split_test: $(SPLITSRC) $(PLANDEPS)
+	@mkdir -p build
+	$(PLANCXX) -o $@ $(SPLITSRC) -lpthread
+
+.PHONY: comm-split-test
+
 # Host sanitizer builds (SURVEY §5 race detection; tests/test_sanitizers.py): the bootstrap, the IPC fd server
 # and the planning code under ASan+UBSan and, separately, TSan. Host code only — no GPU code is instrumented.
 SANCXX   := $(CXX) -g -O1 -fno-omit-frame-pointer -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude
@@ -186,8 +197,12 @@ TSAN     := -fsanitize=thread
 HIPRT    := -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib
 SANBIN   := build/asan/bootstrap_test build/asan/plan_test build/asan/ipc_server_test \
             build/tsan/bootstrap_test build/tsan/ipc_server_test build/asan/bcast_plan_test build/asan/p2p_plan_test \
-            build/asan/rma_plan_test
+            build/asan/rma_plan_test build/asan/comm_split_test build/tsan/comm_split_test
 sanitize: $(SANBIN)
+
+build/asan/comm_split_test build/tsan/comm_split_test: $(SPLITSRC) $(PLANDEPS)
+	@mkdir -p $(dir $@)
+	$(SANCXX) $(if $(findstring asan,$@),$(ASAN),$(TSAN)) -o $@ $(SPLITSRC) -lpthread
 
 build/asan/bootstrap_test build/tsan/bootstrap_test: tests/native/bootstrap_test.cc $(SRCDIR)/bootstrap.cc $(SRCDIR)/debug.cc $(HDRS)
 	@mkdir -p $(dir $@)

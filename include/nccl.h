@@ -71,6 +71,8 @@ typedef enum {
 #define NCCL_CONFIG_UNDEF_INT INT_MIN
 #define NCCL_CONFIG_UNDEF_PTR NULL
 #define NCCL_SPLIT_NOCOLOR -1
+#define NCCL_SHRINK_DEFAULT 0x00 /* the parent is idle: no operation of it is in flight */
+#define NCCL_SHRINK_ABORT 0x01   /* end the parent's operations in flight first (they fail with its abort error) */
 #define NCCL_UNDEF_FLOAT -1.0f
 #define NCCL_API_MAGIC 0xcafebeef
 
@@ -82,7 +84,8 @@ typedef enum {
  * ncclConfig_t built by a caller against the reference header is read correctly here.
  * Fields honoured by this engine: blocking, minCTAs, maxCTAs, commName. The rest are accepted
  * and ignored (their subsystems — CGA clusters, net, collnet, NVLS, RMA — do not exist on the
- * MI355X intra-node path). */
+ * MI355X intra-node path). splitShare and shrinkShare are among the ignored: a child of ncclCommSplit /
+ * ncclCommShrink always owns its staging slab, flags and counters and shares nothing with its parent. */
 typedef struct ncclConfig_v23000 {
   size_t size;
   unsigned int magic;
@@ -186,6 +189,25 @@ ncclResult_t pncclCommInitRankScalable(ncclComm_t* newcomm, int nranks, int myra
 /* nccl.h.in:195 — single-process clique, one comm per device in devlist (NULL = 0..ndev-1). */
 ncclResult_t ncclCommInitAll(ncclComm_t* comm, int ndev, const int* devlist);
 ncclResult_t pncclCommInitAll(ncclComm_t* comm, int ndev, const int* devlist);
+
+/* nccl.h.in:227-240 — child communicators. ncclCommSplit: every rank of comm calls it; the ranks that pass the same
+ * color form one child, ordered by key (ties by their rank in comm); NCCL_SPLIT_NOCOLOR yields *newcomm = NULL.
+ * ncclCommShrink: only the ranks that are not in excludeRanksList call it; the child keeps their order. config NULL
+ * inherits the parent's blocking, minCTAs, maxCTAs and commName. Both calls are synchronous even on a non-blocking
+ * parent: they return ncclSuccess with the child ready, never ncclInProgress; inside ncclGroupStart / ncclGroupEnd
+ * they run at the outermost ncclGroupEnd (how one thread splits every communicator of an ncclCommInitAll clique).
+ * One group holds at most one split or shrink per parent communicator (a second one of the same parent goes into
+ * the next group).
+ * The child is independent of its parent: windows, registrations, user operators are not inherited and either may be
+ * destroyed first. ncclCommShrink on communicators from ncclCommInitRank needs the process that called
+ * ncclGetUniqueId for the parent alive (ncclRemoteError otherwise). Not provided: ncclCommGrow,
+ * ncclCommGetUniqueId, ncclCommRevoke, ncclCommSuspend / ncclCommResume, ncclParam* (DESIGN.md §10.8). */
+ncclResult_t ncclCommSplit(ncclComm_t comm, int color, int key, ncclComm_t* newcomm, ncclConfig_t* config);
+ncclResult_t pncclCommSplit(ncclComm_t comm, int color, int key, ncclComm_t* newcomm, ncclConfig_t* config);
+ncclResult_t ncclCommShrink(ncclComm_t comm, int* excludeRanksList, int excludeRanksCount, ncclComm_t* newcomm,
+                            ncclConfig_t* config, int shrinkFlags);
+ncclResult_t pncclCommShrink(ncclComm_t comm, int* excludeRanksList, int excludeRanksCount, ncclComm_t* newcomm,
+                             ncclConfig_t* config, int shrinkFlags);
 
 /* nccl.h.in:203,207,212 */
 ncclResult_t ncclCommFinalize(ncclComm_t comm);

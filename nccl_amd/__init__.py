@@ -146,10 +146,13 @@ EXPORTED = [
     "ncclCommRegister", "ncclCommDeregister", "ncclCommWindowRegister", "ncclCommWindowDeregister",
     "ncclWinGetUserPtr", "ncclCommInitRankScalable", "ncclCommMemStats", "ncclGroupSimulateEnd",
     "ncclBroadcast", "ncclBcast", "ncclSend", "ncclRecv", "ncclAlltoAll", "ncclGather", "ncclScatter",
-    "ncclPutSignal", "ncclSignal", "ncclWaitSignal",
+    "ncclPutSignal", "ncclSignal", "ncclWaitSignal", "ncclCommSplit", "ncclCommShrink",
 ]
 
 
+SPLIT_NOCOLOR = -1          # nccl.h.in:57
+SHRINK_DEFAULT = 0x00       # nccl.h.in:76-77
+SHRINK_ABORT = 0x01
 WIN_DEFAULT = 0x00          # nccl.h.in:64-68
 WIN_COLL_SYMMETRIC = 0x01
 WIN_STRICT_ORDERING = 0x02
@@ -218,6 +221,8 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "ncclCommInitRankScalable": (R, [ctypes.POINTER(P), I, I, I, ctypes.POINTER(UniqueId), ctypes.POINTER(Config)]),
         "ncclCommMemStats": (R, [P, I, ctypes.POINTER(U64)]),
         "ncclGroupSimulateEnd": (R, [ctypes.POINTER(SimInfo)]),
+        "ncclCommSplit": (R, [P, I, I, ctypes.POINTER(P), ctypes.POINTER(Config)]),
+        "ncclCommShrink": (R, [P, ctypes.POINTER(I), I, ctypes.POINTER(P), ctypes.POINTER(Config), I]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -345,8 +350,11 @@ class Window:
 class Communicator:
     """Mirror of nccl4py's Communicator (bindings/nccl4py/nccl/core/communicator.py:223)."""
 
-    def __init__(self, ptr: int):
-        self._comm = ptr
+    def __init__(self, ptr: Optional[int]):
+        self._h = ctypes.c_void_p(ptr)  # split / shrink inside a group: filled in when the group ends
+        # the child of this communicator's latest split / shrink: inside a group the library writes its handle when the
+        # group ends, so its storage lives at least as long as this parent (one such call per parent and group)
+        self._child = None
         self._nranks = None
         self._rank = None
         self._device = None
@@ -396,7 +404,36 @@ class Communicator:
         _check(lib.ncclCommInitAll(arr, len(devs), dl), "ncclCommInitAll")
         return [cls(arr[i]) for i in range(len(devs))]
 
+    # ---- child communicators (nccl.h.in:227-240) ----
+    def split(self, color: int, key: int = 0, config: Optional[Config] = None) -> Optional["Communicator"]:
+        """ncclCommSplit: every rank of this communicator calls it; ranks passing the same color form one child, ordered
+        by key (ties by rank here). SPLIT_NOCOLOR returns None (the rank still takes part). The call returns with the
+        child ready; inside group() it runs when the group ends (one thread splitting every communicator of an
+        init_all clique), and the returned object is usable from then on. One split or shrink per parent and group."""
+        child = self._child = Communicator(None)
+        _check(load().ncclCommSplit(self._comm, color, key, ctypes.byref(child._h),
+                                    ctypes.byref(config) if config is not None else None), "ncclCommSplit")
+        return None if color == SPLIT_NOCOLOR else child
+
+    def shrink(self, exclude: Sequence[int], flags: int = SHRINK_DEFAULT, config: Optional[Config] = None) -> "Communicator":
+        """ncclCommShrink: called by the ranks that are not in `exclude` (parent ranks, any order); the child keeps
+        their order. SHRINK_ABORT first ends this communicator's operations in flight."""
+        ex = list(exclude)
+        arr = (ctypes.c_int * max(1, len(ex)))(*ex)
+        child = self._child = Communicator(None)
+        _check(load().ncclCommShrink(self._comm, arr if ex else None, len(ex), ctypes.byref(child._h),
+                                     ctypes.byref(config) if config is not None else None, flags), "ncclCommShrink")
+        return child
+
     # ---- properties ----
+    @property
+    def _comm(self) -> int:
+        return self._h.value or 0
+
+    @_comm.setter
+    def _comm(self, v: int) -> None:
+        self._h = ctypes.c_void_p(v)
+
     @property
     def ptr(self) -> int:
         return self._comm

@@ -95,9 +95,19 @@ ncclResult_t bootstrapRelease(const ncclUniqueId* id);  // tell an unused root t
 ncclResult_t bootstrapReleaseUnused(const ncclUniqueId* ids, int nId, int rank, int nranks);  // this rank's share
 ncclResult_t bootstrapAllGather(Bootstrap* b, void* data, size_t bytesPerRank);
 ncclResult_t bootstrapBarrier(Bootstrap* b);
+// a round among the ranks of `mask` only (bit r = rank r); data: one block per participant, in rank order
+ncclResult_t bootstrapAllGatherSubset(Bootstrap* b, uint32_t mask, void* data, size_t bytesPerRank);
+// the rendezvous of ncclCommSplit / ncclCommShrink over the parent's star: the child's id, this rank's place in it
+// and its size (0: NCCL_SPLIT_NOCOLOR); members: the child's parent ranks in child-rank order
+ncclResult_t bootstrapSplit(Bootstrap* b, int color, int key, ncclUniqueId* id, int* childRank, int* childRanks,
+                            std::vector<int>* members = nullptr);
+ncclResult_t bootstrapShrink(Bootstrap* b, uint32_t excludeMask, ncclUniqueId* id, int* childRank, int* childRanks);
+int bootstrapLiveRoots();  // root threads of this process still serving (tests)
 void bootstrapClose(Bootstrap* b);
 std::shared_ptr<LocalClique> cliqueCreate(int nranks);
 ncclResult_t cliqueAllGather(LocalClique* c, int rank, void* data, size_t bytesPerRank);
+// the same when only `expected` of the clique's ranks call (ncclCommShrink); the others' blocks read as zeros
+ncclResult_t cliqueAllGatherAmong(LocalClique* c, int rank, void* data, size_t bytesPerRank, int expected);
 
 // ---------------------------------------------------------------- communicator (reference src/include/comm.h)
 constexpr uint64_t kCommMagic = 0x4d493335584e4343ull;  // "MI35XNCC"
@@ -179,6 +189,13 @@ struct PeerInfo {  // exchanged once at init (reference: struct ncclPeerInfo, sr
   // this rank's fd server (ipc.cc), published on its own: a slab exported by the hipIpc fallback carries no server
   // name in its descriptor, yet the server still maps peers' registered buffers (register.cc)
   char fdServer[40];
+};
+
+// Ranks on one GPU (split.h): a communicator keeps the table of its oldest ancestor, so that a child's channel cap
+// counts the siblings that launch beside it.
+struct GpuOccupancy {
+  char busId[32];
+  int ranks;
 };
 
 struct UserRedOp {  // ncclRedOpCreatePreMulSum state (reference src/enqueue.cc:2560-2576)
@@ -329,6 +346,9 @@ struct ncclComm {
   int rank, nRanks, device;
   bool blocking;
   int minCTAs, maxCTAs;
+  // minCTAs / maxCTAs as the creating call's config gave them (NCCL_CONFIG_UNDEF_INT: not given): what a child made
+  // with a NULL config inherits, so that it is shaped like a communicator created with its parent's config
+  int cfgMinCTAs = NCCL_CONFIG_UNDEF_INT, cfgMaxCTAs = NCCL_CONFIG_UNDEF_INT;
   std::string commName;
 
   ncclamd::Bootstrap* bootstrap = nullptr;
@@ -358,6 +378,9 @@ struct ncclComm {
   int llChannels = 32;      // LL protocol: channels and line bytes per (channel, parity, sender)
   size_t llBytes = 32 << 10;
   int chanCap = 0;  // channels per launch that stay co-resident even with several ranks per GPU
+  // ranks per GPU the cap is computed from: this communicator's own table's, or, for a child of ncclCommSplit /
+  // ncclCommShrink, its parent's (copied down every generation)
+  std::vector<ncclamd::GpuOccupancy> occupancy;
   // Several ranks of this process on this GPU (test mode): their spinning kernels must run concurrently,
   // but HIP multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues, so two user streams
   // can share one queue and serialise the ranks (deadlock until the spin timeout). Such comms launch on

@@ -6,7 +6,9 @@
 // ncclCommDestroy :2879, ncclCommAbort :3025, ncclGetErrorString :3415, ncclCommGetAsyncError :3449),
 // src/enqueue.cc:2479-2583 (user PreMulSum ops), src/allocator.cc (ncclMemAlloc).
 // What is NOT rebuilt (out of scope): topology/graph search (single-node full mesh is
-// fixed), proxy thread, net/SHM/NVLS transports, split/shrink/grow, windows, suspend/resume.
+// fixed), proxy thread, net/SHM/NVLS transports, grow, suspend/resume.
+// Child communicators (ncclCommSplit :3073-3203, ncclCommShrink :3392-3412, commGetSplitInfo :1772-1813) are at the
+// end of this file; DESIGN.md §10.8.
 #include <string.h>
 #include <unistd.h>
 
@@ -14,7 +16,7 @@
 #include <functional>
 #include <thread>
 
-#include "core.h"
+#include "split.h"
 
 namespace ncclamd {
 ncclResult_t exportHandles(ncclComm* comm, PeerInfo* info);
@@ -72,6 +74,8 @@ static void commDefaults(ncclComm* c, int rank, int nranks, int dev, const ncclC
   bool userMax = paramStr("NCCL_MAX_CTAS") != nullptr || paramStr("NCCL_MAX_NCHANNELS") != nullptr;
   if (cfg) {
     if (cfg->blocking != NCCL_CONFIG_UNDEF_INT) c->blocking = cfg->blocking != 0;
+    c->cfgMinCTAs = cfg->minCTAs;
+    c->cfgMaxCTAs = cfg->maxCTAs;
     if (cfg->minCTAs != NCCL_CONFIG_UNDEF_INT) c->minCTAs = cfg->minCTAs;
     if (cfg->maxCTAs != NCCL_CONFIG_UNDEF_INT) {
       c->maxCTAs = cfg->maxCTAs;
@@ -140,15 +144,14 @@ static ncclResult_t fillPeerInfo(ncclComm* comm, PeerInfo* p) {
 // Channels of one launch must all be resident at once on every GPU (a channel spins on the same
 // channel of its peers). With several ranks on one GPU (NCCL_MULTI_RANK_GPU_ENABLE / test boxes) the
 // launches share the CUs, with half the slots kept free as a margin (enqueue.cc coResidentChannelCap).
-// Every rank computes this from the same peer table, so all agree.
+// Every rank computes this from the same peer table, so all agree. A child of ncclCommSplit / ncclCommShrink arrives
+// with its parent's occupancy (identical on every parent rank) and counts with that: its siblings launch beside it.
 static void computeChannelCap(ncclComm* c) {
-  int minCU = 1 << 30, maxPer = 1;
-  for (size_t i = 0; i < c->peers.size(); i++) {
-    int same = 0;
-    for (size_t j = 0; j < c->peers.size(); j++) same += strcmp(c->peers[i].busId, c->peers[j].busId) == 0;
-    if (same > maxPer) maxPer = same;
+  int minCU = 1 << 30;
+  if (c->occupancy.empty()) c->occupancy = gpuOccupancy(c->peers.data(), c->peers.size());
+  const int maxPer = ranksPerGpu(c->occupancy, c->peers.data(), c->peers.size());
+  for (size_t i = 0; i < c->peers.size(); i++)
     if (c->peers[i].numCUs > 0 && c->peers[i].numCUs < minCU) minCU = c->peers[i].numCUs;
-  }
   if (minCU == (1 << 30)) minCU = 256;
   int cap = coResidentChannelCap(minCU, maxPer);
   // diagnostics (set alike on every rank): the shared-GPU cap itself, up to every slot (2 x CUs / ranks per GPU) —
@@ -285,6 +288,64 @@ static ncclResult_t commInitRankAsync(ncclComm** out, int nranks, ncclUniqueId i
   return ncclInProgress;
 }
 
+// The comms of one in-process clique, built by one thread: ncclCommInitAll's, or a child's of ncclCommSplit /
+// ncclCommShrink on such a parent (`inherited`: the parent's GPU occupancy). Each member's config is its own; the
+// shape every rank must agree on is rank 0's, as in commInitRankInto.
+struct CliqueMember {
+  int dev;
+  const ncclConfig_t* cfg;
+};
+static ncclResult_t cliqueBuild(const std::vector<CliqueMember>& members, const std::vector<GpuOccupancy>* inherited,
+                                std::vector<ncclComm*>* out) {
+  const int ndev = (int)members.size();
+  int oldDev = 0;
+  HIPCHECK(hipGetDevice(&oldDev));
+  std::vector<ncclComm*> cs(ndev, nullptr);
+  ncclResult_t res = ncclSuccess;
+  std::vector<PeerInfo> infos(ndev);
+  for (int i = 0; i < ndev && res == ncclSuccess; i++) {
+    cs[i] = new ncclComm();
+    commDefaults(cs[i], i, ndev, members[i].dev, members[i].cfg);
+    if (cs[i]->tune.parseError) {  // NCCL_ALGO / NCCL_PROTO (reference tuning.cc:456-461)
+      res = ncclInvalidUsage;
+      break;
+    }
+    if (i > 0) {
+      cs[i]->maxChannels = cs[i]->maxCTAs = cs[0]->maxChannels;
+      cs[i]->nSlots = cs[0]->nSlots;
+      cs[i]->slotBytes = cs[0]->slotBytes;
+      cs[i]->tune = cs[0]->tune;
+      cs[i]->minCTAs = cs[0]->minCTAs;
+      if (cs[i]->minCTAs > cs[i]->maxCTAs) cs[i]->minCTAs = cs[i]->maxCTAs;
+    }
+    if (inherited) cs[i]->occupancy = *inherited;
+    res = transportSetup(cs[i]);
+    if (res == ncclSuccess) res = fillPeerInfo(cs[i], &infos[i]);
+  }
+  for (int i = 0; i < ndev && res == ncclSuccess; i++) {
+    cs[i]->peers = infos;
+    computeChannelCap(cs[i]);
+    res = transportConnect(cs[i]);
+    if (res == ncclSuccess) res = commAllocDevState(cs[i]);
+    if (res == ncclSuccess) res = tunerLoad(cs[i]);
+  }
+  if (res == ncclSuccess) res = mapCheck(cs);  // every peer pointer carries bytes both ways (mapcheck.cc)
+  (void)hipSetDevice(oldDev);
+  if (res != ncclSuccess) {
+    for (auto* c : cs)
+      if (c) {
+        transportFree(c);
+        delete c;
+      }
+    return res;
+  }
+  auto clique = cliqueCreate(ndev);
+  for (int i = 0; i < ndev; i++) cs[i]->clique = clique;
+  logRuntimeOnce();
+  *out = cs;
+  return ncclSuccess;
+}
+
 }  // namespace ncclamd
 
 using namespace ncclamd;
@@ -403,45 +464,11 @@ NCCL_EXPORT ncclResult_t ncclCommInitAll(ncclComm_t* comms, int ndev, const int*
     seen[d] = 1;
   }
   if (ndev == 0) return ncclSuccess;
-  int oldDev = 0;
-  HIPCHECK(hipGetDevice(&oldDev));
-  std::vector<ncclComm*> cs(ndev, nullptr);
-  ncclResult_t res = ncclSuccess;
-  std::vector<PeerInfo> infos(ndev);
-  for (int i = 0; i < ndev && res == ncclSuccess; i++) {
-    int d = devlist ? devlist[i] : i;
-    cs[i] = new ncclComm();
-    commDefaults(cs[i], i, ndev, d, nullptr);
-    if (cs[i]->tune.parseError) {  // NCCL_ALGO / NCCL_PROTO (reference tuning.cc:456-461)
-      res = ncclInvalidUsage;
-      break;
-    }
-    res = transportSetup(cs[i]);
-    if (res == ncclSuccess) res = fillPeerInfo(cs[i], &infos[i]);
-  }
-  for (int i = 0; i < ndev && res == ncclSuccess; i++) {
-    cs[i]->peers = infos;
-    computeChannelCap(cs[i]);
-    res = transportConnect(cs[i]);
-    if (res == ncclSuccess) res = commAllocDevState(cs[i]);
-    if (res == ncclSuccess) res = tunerLoad(cs[i]);
-  }
-  if (res == ncclSuccess) res = mapCheck(cs);  // every peer pointer carries bytes both ways (mapcheck.cc)
-  (void)hipSetDevice(oldDev);
-  if (res != ncclSuccess) {
-    for (auto* c : cs)
-      if (c) {
-        transportFree(c);
-        delete c;
-      }
-    return res;
-  }
-  auto clique = cliqueCreate(ndev);
-  for (int i = 0; i < ndev; i++) {
-    cs[i]->clique = clique;
-    comms[i] = cs[i];
-  }
-  logRuntimeOnce();
+  std::vector<CliqueMember> members(ndev);
+  for (int i = 0; i < ndev; i++) members[i] = {devlist ? devlist[i] : i, nullptr};
+  std::vector<ncclComm*> cs;
+  NCCLCHECK(cliqueBuild(members, nullptr, &cs));
+  for (int i = 0; i < ndev; i++) comms[i] = cs[i];
   INFO("ncclCommInitAll COMPLETE: %d ranks", ndev);
   return ncclSuccess;
 }
@@ -656,3 +683,217 @@ NCCL_EXPORT ncclResult_t ncclMemFree(void* ptr) {
   return ncclSuccess;
 }
 NCCL_ALIAS(ncclResult_t, ncclMemFree, void*)
+
+// ---- child communicators (reference init.cc:3073-3203 ncclCommSplit, :3392-3412 ncclCommShrink) ----
+namespace ncclamd {
+
+// What one parent rank brings to the rendezvous (copied when the call is deferred to ncclGroupEnd).
+struct ChildRequest {
+  ncclComm* parent;
+  ncclComm** out;
+  bool shrink;
+  int color, key;        // split
+  uint32_t excludeMask;  // shrink: bit r = parent rank r is excluded
+  bool abortFirst;       // NCCL_SHRINK_ABORT
+  bool hasCfg;
+  ncclConfig_t cfg;
+  std::string name;      // cfg.commName, copied: the caller's string may be gone at ncclGroupEnd
+};
+
+// The child's config: the caller's, or the parent's blocking, minCTAs, maxCTAs and commName as its creator gave them.
+static ncclConfig_t childConfig(const ChildRequest& rq) {
+  ncclConfig_t c = NCCL_CONFIG_INITIALIZER;
+  const ncclComm* p = rq.parent;
+  if (rq.hasCfg) {
+    c = rq.cfg;
+    c.commName = rq.name.empty() ? nullptr : rq.name.c_str();
+  } else {
+    c.blocking = p->blocking ? 1 : 0;
+    c.minCTAs = p->cfgMinCTAs;
+    c.maxCTAs = p->cfgMaxCTAs;
+    c.commName = p->commName.empty() ? nullptr : p->commName.c_str();
+  }
+  return c;
+}
+
+// Parent with a TCP bootstrap: rendezvous over its star, then an ordinary init on the child's own id.
+static ncclResult_t childOverBootstrap(const ChildRequest& rq, const ncclConfig_t& cfg) {
+  ncclComm* p = rq.parent;
+  ncclUniqueId id;
+  int crank = 0, cn = 0;
+  if (rq.shrink) NCCLCHECK(bootstrapShrink(p->bootstrap, rq.excludeMask, &id, &crank, &cn));
+  else NCCLCHECK(bootstrapSplit(p->bootstrap, rq.color, rq.key, &id, &crank, &cn));
+  if (cn == 0) return ncclSuccess;  // NCCL_SPLIT_NOCOLOR
+  ncclComm* c = new ncclComm();
+  commDefaults(c, crank, cn, p->device, &cfg);
+  c->occupancy = p->occupancy;
+  ncclResult_t res = commInitRankInto(c, cn, id, crank, p->device);
+  if (res != ncclSuccess) {
+    c->startMagic = c->endMagic = 0;
+    delete c;
+    return res;
+  }
+  *rq.out = c;
+  return ncclSuccess;
+}
+
+// Parent from ncclCommInitAll: rendezvous on its LocalClique (every calling rank on a thread of its own). The first
+// round gathers the requests; each child's rank 0 then builds that child's whole clique (cliqueBuild, one mapping
+// check over its members) while the others wait in the second round, which hands every rank its communicator.
+struct CliqueAsk {
+  int present, shrink, color, key, dev;
+  uint32_t excludeMask;
+  const ncclConfig_t* cfg;  // in the asking thread's frame, which waits in the second round while the builder reads it
+};
+struct CliqueAnswer {
+  int result;
+  ncclComm* kids[NCCL_AMD_MAX_RANKS];
+};
+static ncclResult_t childOverClique(const ChildRequest& rq, const ncclConfig_t& cfg) {
+  ncclComm* p = rq.parent;
+  const int n = p->nRanks, me = p->rank;
+  const int expected = rq.shrink ? n - __builtin_popcount(rq.excludeMask) : n;
+  std::vector<CliqueAsk> asks(n);
+  memset(asks.data(), 0, n * sizeof(CliqueAsk));
+  asks[me] = {1, rq.shrink ? 1 : 0, rq.color, rq.key, p->device, rq.excludeMask, &cfg};
+  NCCLCHECK(cliqueAllGatherAmong(p->clique.get(), me, asks.data(), sizeof(CliqueAsk), expected));
+  // every caller sees the same table, so a mismatch fails them all alike, before anything is built
+  for (int r = 0; r < n; r++) {
+    const bool want = !rq.shrink || !((rq.excludeMask >> r) & 1);
+    if ((asks[r].present != 0) != want || (asks[r].present && (asks[r].shrink != asks[me].shrink ||
+                                                               asks[r].excludeMask != asks[me].excludeMask))) {
+      WARN("%s: the ranks of the parent do not agree on the call (rank %d)", rq.shrink ? "ncclCommShrink" : "ncclCommSplit", r);
+      return ncclInvalidUsage;
+    }
+  }
+  std::vector<int> mem;
+  if (rq.shrink) {
+    for (int r = 0; r < n; r++)
+      if (asks[r].present) mem.push_back(r);
+  } else {
+    std::vector<int> colors(n), keys(n);
+    for (int r = 0; r < n; r++) {
+      colors[r] = asks[r].color;
+      keys[r] = asks[r].key;
+    }
+    mem = splitMembers(colors.data(), keys.data(), n, rq.color);
+  }
+  std::vector<CliqueAnswer> ans(n);
+  memset(ans.data(), 0, n * sizeof(CliqueAnswer));
+  if (!mem.empty() && mem[0] == me) {
+    std::vector<CliqueMember> members;
+    for (int r : mem) members.push_back({asks[r].dev, asks[r].cfg});
+    std::vector<ncclComm*> kids;
+    ans[me].result = (int)cliqueBuild(members, &p->occupancy, &kids);
+    for (size_t i = 0; i < kids.size(); i++) ans[me].kids[i] = kids[i];
+  }
+  NCCLCHECK(cliqueAllGatherAmong(p->clique.get(), me, ans.data(), sizeof(CliqueAnswer), expected));
+  if (mem.empty()) return ncclSuccess;  // NCCL_SPLIT_NOCOLOR
+  const CliqueAnswer& a = ans[mem[0]];
+  if (a.result != ncclSuccess) return (ncclResult_t)a.result;
+  for (size_t i = 0; i < mem.size(); i++)
+    if (mem[i] == me) *rq.out = a.kids[i];
+  return ncclSuccess;
+}
+
+static ncclResult_t commChild(const ChildRequest& rq) {
+  ncclComm* p = rq.parent;
+  DeviceRestore restore;
+  HIPCHECK(hipSetDevice(p->device));
+  if (rq.abortFirst) {
+    // kernels of the parent still in flight end with DERR_ABORT (its async error stays set); an idle parent is untouched
+    if (p->hostAbort) __atomic_store_n(p->hostAbort, 1u, __ATOMIC_RELEASE);
+    HIPCHECK(hipDeviceSynchronize());
+    if (p->hostAbort) __atomic_store_n(p->hostAbort, 0u, __ATOMIC_RELEASE);
+  }
+  const ncclConfig_t cfg = childConfig(rq);
+  ncclResult_t res = p->bootstrap ? childOverBootstrap(rq, cfg) : p->clique ? childOverClique(rq, cfg) : ncclInternalError;
+  // (a NCCL_SPLIT_NOCOLOR call's newcomm was set to NULL when the call was made and is not touched again)
+  if (res == ncclSuccess && (rq.shrink || rq.color != NCCL_SPLIT_NOCOLOR) && *rq.out)
+    INFO("comm %p rank %d nRanks %d: child of comm %p rank %d nRanks %d (%s); slot %zu bytes, channel cap %d (parent %d)",
+         (void*)*rq.out, (*rq.out)->rank, (*rq.out)->nRanks, (void*)p, p->rank, p->nRanks, rq.shrink ? "shrink" : "split",
+         (*rq.out)->slotBytes, (*rq.out)->chanCap, p->chanCap);
+  return res;
+}
+
+// Synchronous even for a non-blocking parent: returns with the child ready, never ncclInProgress. Inside a group the
+// call is deferred and runs beside the group's other inits at the outermost ncclGroupEnd. One group holds at most one
+// split or shrink per parent: the deferred calls run side by side, and two of one parent would mix their rounds on
+// the parent's one socket or clique (the caller's to keep, like the reference's one-call-at-a-time rule per comm).
+static ncclResult_t childCommon(ChildRequest& rq, ncclConfig_t* config) {
+  NCCLCHECK(checkConfig(config));
+  if (rq.parent->asyncResult.load() == ncclInProgress) {
+    WARN("%s : the parent communicator is still initialising", rq.shrink ? "ncclCommShrink" : "ncclCommSplit");
+    return ncclInvalidUsage;
+  }
+  *rq.out = nullptr;
+  rq.hasCfg = config != nullptr;
+  if (config) {
+    rq.cfg = *config;
+    if (config->commName) rq.name = config->commName;
+  }
+  ipcDrainReleases();
+  if (groupActive()) return groupDeferInit([rq]() -> ncclResult_t { return commChild(rq); });
+  return commChild(rq);
+}
+
+}  // namespace ncclamd
+
+static ncclResult_t commSplitImpl(ncclComm_t comm, int color, int key, ncclComm_t* newcomm, ncclConfig_t* config) {
+  logInit();
+  NCCLCHECK(commCheck(comm, "ncclCommSplit", "comm"));
+  if (newcomm == nullptr) {
+    WARN("ncclCommSplit : newcomm argument is NULL");
+    return ncclInvalidArgument;
+  }
+  ROCTX_RANGE("ncclCommSplit color=%d key=%d", color, key);
+  ChildRequest rq = {};
+  rq.parent = comm;
+  rq.out = newcomm;
+  rq.color = color;  // only NCCL_SPLIT_NOCOLOR makes no child: other negative colours are colours (reference :1786)
+  rq.key = key;
+  return childCommon(rq, config);
+}
+// a call that fails its checks inside a group fails the group (reference ncclGroupErrCheck, init.cc:3402)
+NCCL_EXPORT ncclResult_t ncclCommSplit(ncclComm_t comm, int color, int key, ncclComm_t* newcomm, ncclConfig_t* config) {
+  const ncclResult_t res = commSplitImpl(comm, color, key, newcomm, config);
+  groupRecordError(res);
+  return res;
+}
+NCCL_ALIAS(ncclResult_t, ncclCommSplit, ncclComm_t, int, int, ncclComm_t*, ncclConfig_t*)
+
+static ncclResult_t commShrinkImpl(ncclComm_t comm, int* excludeRanksList, int excludeRanksCount, ncclComm_t* newcomm,
+                                   ncclConfig_t* config, int shrinkFlags) {
+  logInit();
+  NCCLCHECK(commCheck(comm, "ncclCommShrink", "comm"));
+  if (newcomm == nullptr) {
+    WARN("ncclCommShrink : newcomm argument is NULL");
+    return ncclInvalidArgument;
+  }
+  if (excludeRanksList == nullptr || excludeRanksCount <= 0) {
+    WARN("ncclCommShrink : excludeRanksList is NULL or excludeRanksCount %d <= 0", excludeRanksCount);
+    return ncclInvalidArgument;
+  }
+  ChildRequest rq = {};
+  for (int i = 0; i < excludeRanksCount; i++) {
+    const int r = excludeRanksList[i];
+    if (r < 0 || r >= comm->nRanks || r == comm->rank) {
+      WARN("ncclCommShrink : excluded rank %d is %s", r, r == comm->rank ? "the caller itself" : "out of range");
+      return ncclInvalidArgument;
+    }
+    rq.excludeMask |= 1u << r;
+  }
+  ROCTX_RANGE("ncclCommShrink exclude=0x%x flags=%d", rq.excludeMask, shrinkFlags);
+  rq.parent = comm;
+  rq.out = newcomm;
+  rq.shrink = true;
+  rq.abortFirst = (shrinkFlags & NCCL_SHRINK_ABORT) != 0;
+  return childCommon(rq, config);
+}
+NCCL_EXPORT ncclResult_t ncclCommShrink(ncclComm_t comm, int* excludeRanksList, int excludeRanksCount, ncclComm_t* newcomm,
+                                        ncclConfig_t* config, int shrinkFlags) {
+  const ncclResult_t res = commShrinkImpl(comm, excludeRanksList, excludeRanksCount, newcomm, config, shrinkFlags);
+  groupRecordError(res);
+  return res;
+}
+NCCL_ALIAS(ncclResult_t, ncclCommShrink, ncclComm_t, int*, int, ncclComm_t*, ncclConfig_t*, int)
