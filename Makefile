@@ -16,15 +16,16 @@ EXTRA    ?=
 COMMON   := -O3 -fPIC -std=c++17 -ffp-contract=off -fvisibility=hidden -Wall -Wno-unused-function \
             -Wno-unused-variable -Wno-unused-but-set-variable -Iinclude $(EXTRA)
 HIPFLAGS := $(COMMON) --offload-arch=$(ARCH) -fno-gpu-flush-denormals-to-zero -munsafe-fp-atomics
-HOSTSRC  := debug.cc bootstrap.cc ipc.cc transport.cc init.cc group.cc enqueue.cc p2p.cc rma.cc register.cc tuner.cc mapcheck.cc
+HOSTSRC  := debug.cc bootstrap.cc ipc.cc transport.cc init.cc group.cc enqueue.cc p2p.cc rma.cc register.cc tuner.cc mapcheck.cc \
+            devcomm.cc
 HOSTOBJ  := $(HOSTSRC:%.cc=$(BUILD)/%.o)
 DEVSRC   := $(notdir $(wildcard $(SRCDIR)/*.hip))
 DEVOBJ   := $(DEVSRC:%.hip=$(BUILD)/%.o)
-HDRS     := $(wildcard $(SRCDIR)/*.h) include/nccl.h
+HDRS     := $(wildcard $(SRCDIR)/*.h) include/nccl.h include/nccl_device.h
 
 all: lib oracle numerics-host bootstrap-test tuner-test nccl-perf comm-examples plan-test mapcheck-test xgmi-probe atomicity-probe \
      fp8-probe release-probe reuse-probe export-check-test barrier-probe bcast-plan-test bcast-example p2p-plan-test sendrecv-example \
-     rma-plan-test sym-a2a-plan-test comm-split-test
+     rma-plan-test sym-a2a-plan-test comm-split-test devapi-kernels devapi-layout-test devapi-example
 
 .PHONY: export-check-test
 export-check-test: tests/native/export_check_test
@@ -177,6 +178,31 @@ tests/native/sendrecv_example: tests/native/sendrecv_example.cc include/nccl.h $
 	$(HIPCC) -O2 --offload-arch=$(ARCH) -Iinclude -o $@ $< -L$(LIBDIR) -lnccl -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
 .PHONY: sendrecv-example
+
+# The device API (include/nccl_device.h). Test kernels written against the two public headers only, driven
+# through ctypes by tests/test_gpu_device_api.py; a CPU sweep of the header's pure functions (resource layout, teams,
+# epoch compare), a stand-alone host program under ASan+UBSan; the reference's LSA AllReduce example restated against
+# the C ABI, one pthread per rank (with a timing mode, profiles/README.md).
+DEVAPIHDRS := include/nccl.h include/nccl_device.h
+devapi-kernels: tests/native/libdevapi_kernels.so
+
+tests/native/libdevapi_kernels.so: tests/native/devapi_kernels.hip $(DEVAPIHDRS) $(LIBDIR)/libnccl.so
+	$(HIPCC) -O3 -std=c++17 -fPIC -shared -fvisibility=hidden --offload-arch=$(ARCH) -fno-gpu-flush-denormals-to-zero \
+	  -ffp-contract=off -Iinclude -o $@ $< -L$(LIBDIR) -lnccl -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
+
+devapi-layout-test: tests/native/devapi_layout_test
+
+tests/native/devapi_layout_test: tests/native/devapi_layout_test.cc $(DEVAPIHDRS)
+	$(CXX) -g -O1 -fno-omit-frame-pointer -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude \
+	  -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
+
+devapi-example: tests/native/devapi_example
+
+tests/native/devapi_example: tests/native/devapi_example.hip $(DEVAPIHDRS) $(LIBDIR)/libnccl.so
+	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude -o $@ $< -L$(LIBDIR) -lnccl -lpthread \
+	  -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
+
+.PHONY: devapi-kernels devapi-layout-test devapi-example
 
 # CPU test of ncclCommSplit / ncclCommShrink below the GPU: membership and inherited occupancy (split.h), the channel
 # cap they feed (enqueue.cc, its launches stubbed) and the subset rounds and rendezvous of the bootstrap, ranks as threads

@@ -388,6 +388,27 @@ typedef struct ncclSimInfo_v22200 {
 ncclResult_t ncclGroupSimulateEnd(ncclSimInfo_t* simInfo);
 ncclResult_t pncclGroupSimulateEnd(ncclSimInfo_t* simInfo);
 
+/* ---- Device API, host entry points (reference src/include/nccl_device/core.h:194-205) ----
+ * The structs are defined in include/nccl_device.h (C++ / HIP), which also holds the device side: window pointers,
+ * teams and LSA barriers for the caller's own kernels. ncclDevCommCreate is collective over the
+ * communicator, every rank passing the same requirements; inside a group it runs at the outermost ncclGroupEnd, like
+ * ncclCommWindowRegister, and *outDevComm is filled then. It works on children of ncclCommSplit / ncclCommShrink too.
+ * Several DevComms of one communicator may be alive at once; ncclDevCommDestroy, ncclCommDestroy and ncclCommAbort
+ * release them. The pointer getters bound `offset` by the bytes the peer registered and the rank by the rank count. */
+typedef struct ncclDevComm ncclDevComm_t;
+typedef struct ncclDevCommRequirements ncclDevCommRequirements_t;
+typedef struct ncclCommProperties ncclCommProperties_t;
+ncclResult_t ncclCommQueryProperties(ncclComm_t comm, ncclCommProperties_t* props);
+ncclResult_t pncclCommQueryProperties(ncclComm_t comm, ncclCommProperties_t* props);
+ncclResult_t ncclDevCommCreate(ncclComm_t comm, const ncclDevCommRequirements_t* reqs, ncclDevComm_t* outDevComm);
+ncclResult_t pncclDevCommCreate(ncclComm_t comm, const ncclDevCommRequirements_t* reqs, ncclDevComm_t* outDevComm);
+ncclResult_t ncclDevCommDestroy(ncclComm_t comm, const ncclDevComm_t* devComm);
+ncclResult_t pncclDevCommDestroy(ncclComm_t comm, const ncclDevComm_t* devComm);
+ncclResult_t ncclGetLsaDevicePointer(ncclWindow_t window, size_t offset, int lsaRank, void** outPtr);
+ncclResult_t pncclGetLsaDevicePointer(ncclWindow_t window, size_t offset, int lsaRank, void** outPtr);
+ncclResult_t ncclGetPeerDevicePointer(ncclWindow_t window, size_t offset, int peer, void** outPtr);
+ncclResult_t pncclGetPeerDevicePointer(ncclWindow_t window, size_t offset, int peer, void** outPtr);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,110 @@ class Config(ctypes.Structure):  # ncclConfig_t, nccl.h.in:84-108
         return c
 
 
+class DevResourceRequirements(ctypes.Structure):  # ncclDevResourceRequirements, include/nccl_device.h
+    pass
+
+
+DevResourceRequirements._fields_ = [
+    ("next", ctypes.POINTER(DevResourceRequirements)), ("bufferSize", ctypes.c_size_t), ("bufferAlign", ctypes.c_size_t),
+    ("outBufferHandle", ctypes.POINTER(ctypes.c_uint32)), ("ginSignalCount", ctypes.c_int),
+    ("ginCounterCount", ctypes.c_int), ("outGinSignalStart", ctypes.c_void_p), ("outGinCounterStart", ctypes.c_void_p),
+]
+
+
+class DevCommRequirements(ctypes.Structure):  # ncclDevCommRequirements, include/nccl_device.h
+    _fields_ = [
+        ("size", ctypes.c_size_t), ("magic", ctypes.c_uint), ("version", ctypes.c_uint),
+        ("resourceRequirementsList", ctypes.POINTER(DevResourceRequirements)), ("teamRequirementsList", ctypes.c_void_p),
+        ("lsaMultimem", ctypes.c_bool), ("barrierCount", ctypes.c_int), ("lsaBarrierCount", ctypes.c_int),
+        ("railGinBarrierCount", ctypes.c_int), ("lsaLLA2ABlockCount", ctypes.c_int), ("lsaLLA2ASlotCount", ctypes.c_int),
+        ("ginForceEnable", ctypes.c_bool), ("ginContextCount", ctypes.c_int), ("ginSignalCount", ctypes.c_int),
+        ("ginCounterCount", ctypes.c_int), ("ginConnectionType", ctypes.c_int), ("ginExclusiveContexts", ctypes.c_bool),
+        ("ginQueueDepth", ctypes.c_int), ("ginTrafficClass", ctypes.c_int), ("worldGinBarrierCount", ctypes.c_int),
+        ("ginStrongSignalsRequired", ctypes.c_bool), ("ginVaSignalsRequired", ctypes.c_bool),
+    ]
+
+    @classmethod
+    def default(cls, **kw) -> "DevCommRequirements":
+        """NCCL_DEV_COMM_REQUIREMENTS_INITIALIZER, then the given fields."""
+        q = cls()
+        q.size = ctypes.sizeof(cls)
+        q.magic = 0xCAFEBEEF
+        q.version = get_version_code_static()
+        q.ginContextCount = 4
+        q.ginTrafficClass = -(2 ** 31)
+        q.ginStrongSignalsRequired = q.ginVaSignalsRequired = True
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return q
+
+
+class CommProperties(ctypes.Structure):  # ncclCommProperties, include/nccl_device.h
+    _fields_ = [
+        ("size", ctypes.c_size_t), ("magic", ctypes.c_uint), ("version", ctypes.c_uint),
+        ("rank", ctypes.c_int), ("nRanks", ctypes.c_int), ("cudaDev", ctypes.c_int), ("nvmlDev", ctypes.c_int),
+        ("deviceApiSupport", ctypes.c_bool), ("multimemSupport", ctypes.c_bool), ("ginType", ctypes.c_int),
+        ("nLsaTeams", ctypes.c_int), ("hostRmaSupport", ctypes.c_bool), ("railedGinType", ctypes.c_int),
+    ]
+
+    @classmethod
+    def default(cls) -> "CommProperties":
+        p = cls()
+        p.size = ctypes.sizeof(cls)
+        p.magic = 0xCAFEBEEF
+        p.version = get_version_code_static()
+        return p
+
+
+DEV_MAX_RANKS = 16              # NCCL_DEVICE_MAX_RANKS
+DEV_MAX_LSA_BARRIERS = 4096     # NCCL_DEVICE_MAX_LSA_BARRIERS
+DEV_RESOURCE_GRANULE = 128      # NCCL_DEVICE_RESOURCE_GRANULE
+
+
+class DevCommStruct(ctypes.Structure):
+    """ncclDevComm (include/nccl_device.h), handed to kernels by value. Opaque to Python callers except for the
+    fields a test or a launcher may want to read."""
+    _fields_ = [
+        ("magic", ctypes.c_uint), ("version", ctypes.c_uint), ("rank", ctypes.c_int), ("nRanks", ctypes.c_int),
+        ("lsaRank", ctypes.c_int), ("lsaSize", ctypes.c_int), ("resourceWindow", ctypes.c_void_p),
+        ("resourcePeerPtr", ctypes.c_void_p * DEV_MAX_RANKS), ("lsaBarrierBufHandle", ctypes.c_uint32),
+        ("lsaBarrierCount", ctypes.c_int), ("abortFlag", ctypes.c_void_p), ("errorWord", ctypes.c_void_p),
+        ("timeoutTicks", ctypes.c_uint64), ("hostState", ctypes.c_void_p),
+    ]
+
+
+class DevComm:
+    """What Communicator.dev_comm_create returns: the ncclDevComm struct (`struct`, pass ctypes.byref(d.struct) or
+    d.ptr to a launcher taking `const ncclDevComm*`) and the resource-buffer handles in the order asked."""
+
+    def __init__(self, comm: "Communicator", lsa_barriers: int, buffers):
+        self.comm = comm
+        self.struct = DevCommStruct()
+        self.lsa_barriers = lsa_barriers
+        self._handles = (ctypes.c_uint32 * max(1, len(buffers)))()
+        self._nbuf = len(buffers)
+        self._reqs = (DevResourceRequirements * max(1, len(buffers)))()
+        for k, (size, align) in enumerate(buffers):
+            r = self._reqs[k]
+            r.bufferSize, r.bufferAlign = size, align
+            r.outBufferHandle = ctypes.cast(ctypes.byref(self._handles, 4 * k), ctypes.POINTER(ctypes.c_uint32))
+            if k + 1 < len(buffers):
+                r.next = ctypes.pointer(self._reqs[k + 1])
+
+    @property
+    def ptr(self) -> int:
+        return ctypes.addressof(self.struct)
+
+    @property
+    def buffer_handles(self) -> list:
+        """ncclDevResourceHandle of every buffer (valid once the creation ran: after the group, inside one)."""
+        return [int(self._handles[k]) for k in range(self._nbuf)]
+
+    @property
+    def resource_window(self) -> int:
+        return self.struct.resourceWindow or 0
+
+
 def get_version_code_static() -> int:
     return 2 * 10000 + 30 * 100 + 7  # NCCL_VERSION(2,30,7)
 
@@ -147,6 +251,8 @@ EXPORTED = [
     "ncclWinGetUserPtr", "ncclCommInitRankScalable", "ncclCommMemStats", "ncclGroupSimulateEnd",
     "ncclBroadcast", "ncclBcast", "ncclSend", "ncclRecv", "ncclAlltoAll", "ncclGather", "ncclScatter",
     "ncclPutSignal", "ncclSignal", "ncclWaitSignal", "ncclCommSplit", "ncclCommShrink",
+    "ncclCommQueryProperties", "ncclDevCommCreate", "ncclDevCommDestroy", "ncclGetLsaDevicePointer",
+    "ncclGetPeerDevicePointer",
 ]
 
 
@@ -223,6 +329,11 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
         "ncclGroupSimulateEnd": (R, [ctypes.POINTER(SimInfo)]),
         "ncclCommSplit": (R, [P, I, I, ctypes.POINTER(P), ctypes.POINTER(Config)]),
         "ncclCommShrink": (R, [P, ctypes.POINTER(I), I, ctypes.POINTER(P), ctypes.POINTER(Config), I]),
+        "ncclCommQueryProperties": (R, [P, ctypes.POINTER(CommProperties)]),
+        "ncclDevCommCreate": (R, [P, ctypes.POINTER(DevCommRequirements), ctypes.POINTER(DevCommStruct)]),
+        "ncclDevCommDestroy": (R, [P, ctypes.POINTER(DevCommStruct)]),
+        "ncclGetLsaDevicePointer": (R, [P, S, I, ctypes.POINTER(P)]),
+        "ncclGetPeerDevicePointer": (R, [P, S, I, ctypes.POINTER(P)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -345,6 +456,12 @@ class Window:
     @property
     def handle(self) -> int:
         return self._h.value or 0
+
+    def lsa_pointer(self, offset: int, rank: int) -> int:
+        """ncclGetLsaDevicePointer: byte `offset` of rank `rank`'s part of this window as mapped in this process."""
+        p = ctypes.c_void_p()
+        _check(load().ncclGetLsaDevicePointer(self.handle, offset, rank, ctypes.byref(p)), "ncclGetLsaDevicePointer")
+        return p.value or 0
 
 
 class Communicator:
@@ -654,6 +771,27 @@ class Communicator:
         p = ctypes.c_void_p()
         _check(load().ncclWinGetUserPtr(self._comm, h, ctypes.byref(p)), "ncclWinGetUserPtr")
         return p.value or 0
+
+    # ---- device API (include/nccl_device.h) ----
+    def query_properties(self) -> CommProperties:
+        """ncclCommQueryProperties."""
+        p = CommProperties.default()
+        _check(load().ncclCommQueryProperties(self._comm, ctypes.byref(p)), "ncclCommQueryProperties")
+        return p
+
+    def dev_comm_create(self, lsa_barriers: int = 0, buffers=(), requirements: Optional[DevCommRequirements] = None) -> DevComm:
+        """ncclDevCommCreate (collective: every rank calls it with the same arguments; one thread driving several
+        ranks calls it inside group(), and the struct and handles are filled in when the group ends). `buffers` is a
+        sequence of (size, align) resource buffers; `requirements` overrides the struct built from the two."""
+        d = DevComm(self, lsa_barriers, list(buffers))
+        q = requirements if requirements is not None else DevCommRequirements.default(lsaBarrierCount=lsa_barriers)
+        if requirements is None and d._nbuf:
+            q.resourceRequirementsList = ctypes.pointer(d._reqs[0])
+        _check(load().ncclDevCommCreate(self._comm, ctypes.byref(q), ctypes.byref(d.struct)), "ncclDevCommCreate")
+        return d
+
+    def dev_comm_destroy(self, dev_comm: DevComm) -> None:
+        _check(load().ncclDevCommDestroy(self._comm, ctypes.byref(dev_comm.struct)), "ncclDevCommDestroy")
 
     # ---- custom operators ----
     def create_pre_mul_sum(self, scalar, dtype: int, device_scalar_ptr: Optional[int] = None) -> int:

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/nccl.h"
+#include "../../include/nccl_device.h"
 #include "device_abi.h"
 
 #define NCCL_EXPORT extern "C" __attribute__((visibility("default")))
@@ -327,18 +328,13 @@ int coResidentChannelCap(int minCUs, int ranksPerGpu);  // enqueue.cc: channels 
 void resolveLinkChannels(CommTuning* t, int nranks, bool userMaxCTAs);
 
 struct ncclCommImpl;
+struct DevCommState;  // devcomm.cc
 }  // namespace ncclamd
 
-// A registered window (reference struct ncclWindow_vidmem / ncclDevrWindow, src/dev_runtime.cc).
-struct ncclWindow_vidmem {
-  ncclComm* comm;
-  void* userPtr;
-  size_t size;
-  int flags;
-  char* peerPtr[NCCL_AMD_MAX_RANKS];  // every rank's window base as mapped in this process
-  size_t peerSize[NCCL_AMD_MAX_RANKS];  // the bytes each rank registered (ncclPutSignal's bound; equal when symmetric)
-  uint64_t peerBase[NCCL_AMD_MAX_RANKS];  // allocation bases of IPC-mapped peers (0: direct pointer)
-};
+// A registered window (reference struct ncclWindow_vidmem / ncclDevrWindow, src/dev_runtime.cc): defined in
+// include/nccl_device.h, because the caller's kernels read its table (peerPtr, peerSize, nRanks, rank). Registered
+// windows live in pinned, mapped, portable host memory (register.cc windowAlloc), as hostAbort does.
+static_assert(NCCL_DEVICE_MAX_RANKS == NCCL_AMD_MAX_RANKS, "the public window table holds one entry per rank");
 
 // The opaque handle type of the public header.
 struct ncclComm {
@@ -392,6 +388,7 @@ struct ncclComm {
 
   std::shared_ptr<ncclamd::LocalClique> clique;  // ncclCommInitAll comms: in-process all-gather
   std::vector<ncclWindow_vidmem*> windows;        // registered windows (register.cc)
+  std::vector<ncclamd::DevCommState*> devComms;   // live ncclDevCommCreate resources (devcomm.cc)
   std::vector<ncclamd::IpcMapping> ipcMaps;
   std::vector<ncclamd::RegHandle*> regHandles;     // ncclCommRegister handles
   std::vector<ncclamd::RegAlloc*> regs;            // registered allocations (register.cc)
@@ -563,6 +560,15 @@ ncclWindow_vidmem* findSymWindow(ncclComm* comm, const void* p, size_t bytes);
 // With `eager` (NCCL_AMD_EAGER_REGISTER=1 and an eligible op), unregistered allocations are registered here too.
 bool regLookup(ncclComm* comm, hipStream_t stream, const void* send, size_t sendBytes, const void* recv,
                size_t recvBytes, const char** rmtSend, char** rmtRecv, bool eager = false);
+// ncclCommWindowRegister's body (collective); ncclDevCommCreate registers its resource allocation through it
+ncclResult_t windowRegister(ncclComm* comm, void* buff, size_t size, ncclWindow_t* win, int flags);
+// drop one window: off the communicator's list, its peers' mappings released, its handle freed
+void windowDrop(ncclComm* comm, ncclWindow_vidmem* w);
+// device API resources (devcomm.cc): the bytes live DevComms hold (ncclCommMemStats); freeing them all at teardown,
+// after windowsFree released their windows
+size_t devCommBytes(const ncclComm* comm);
+bool devCommOwnsWindow(const ncclComm* comm, const ncclWindow_vidmem* w);  // a live DevComm's resource window
+void devCommsFree(ncclComm* comm);
 // release every window and IPC mapping (destroy: also asks peers to unmap this rank's registrations; abort: not)
 void windowsFree(ncclComm* comm, bool notifyPeers);
 // at init: one plain allocation per rank registered with and read back by every peer; any failure turns the eager

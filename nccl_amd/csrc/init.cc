@@ -506,6 +506,7 @@ static ncclResult_t commFree(ncclComm* comm, bool notifyPeers) {
   if (comm->initThread.joinable()) comm->initThread.join();  // a non-blocking init still running
   tunerUnload(comm);
   windowsFree(comm, notifyPeers);
+  devCommsFree(comm);  // the resource allocations of live DevComms (their windows went above)
   if (comm->internalStream) (void)hipStreamDestroy(comm->internalStream);
   if (comm->evIn) (void)hipEventDestroy(comm->evIn);
   if (comm->evOut) (void)hipEventDestroy(comm->evOut);
@@ -620,7 +621,7 @@ NCCL_EXPORT ncclResult_t ncclCommMemStats(ncclComm_t comm, ncclCommMemStat_t sta
   if (st != ncclSuccess) return (ncclResult_t)st;
   switch (stat) {
     case ncclStatGpuMemTotal:
-    case ncclStatGpuMemPersist: *value = commDeviceBytes(comm); return ncclSuccess;
+    case ncclStatGpuMemPersist: *value = commDeviceBytes(comm) + devCommBytes(comm); return ncclSuccess;
     case ncclStatGpuMemSuspend:
     case ncclStatGpuMemSuspended: *value = 0; return ncclSuccess;
     default: return ncclInvalidArgument;

@@ -40,6 +40,7 @@ struct WinInfo {  // exchanged by ncclCommWindowRegister
   uint64_t ptr;      // user pointer (valid in the owner's process)
   uint64_t base;     // its allocation's base
   uint64_t size;
+  int noHandle;      // this rank could not allocate its window handle: the registration fails on every rank
   IpcDesc desc;      // the whole allocation, exported to other processes (ipc.cc)
 };
 
@@ -71,7 +72,24 @@ static void ipcUnmap(ncclComm* comm, int peer, uint64_t base) {
 
 static void windowRelease(ncclComm* comm, ncclWindow_vidmem* w);
 
-static ncclResult_t windowRegister(ncclComm* comm, void* buff, size_t size, ncclWindow_t* win, int flags) {
+// A window handle the caller's kernels dereference (include/nccl_device.h): pinned, mapped, portable host memory,
+// which host and device reach through one address, zero-filled.
+static ncclResult_t windowAlloc(ncclWindow_vidmem** out) {
+  void* p = nullptr;
+  HIPCHECK(hipHostMalloc(&p, sizeof(ncclWindow_vidmem), hipHostMallocMapped | hipHostMallocPortable));
+  void* dev = nullptr;
+  if (hipHostGetDevicePointer(&dev, p, 0) != hipSuccess || dev != p) {
+    (void)hipGetLastError();
+    (void)hipHostFree(p);
+    WARN("ncclCommWindowRegister: the window handle's host memory is not device-visible at its own address");
+    return ncclUnhandledCudaError;
+  }
+  memset(p, 0, sizeof(ncclWindow_vidmem));
+  *out = (ncclWindow_vidmem*)p;
+  return ncclSuccess;
+}
+
+ncclResult_t windowRegister(ncclComm* comm, void* buff, size_t size, ncclWindow_t* win, int flags) {
   HIPCHECK(hipSetDevice(comm->device));
   std::vector<WinInfo> all(comm->nRanks);
   WinInfo& me = all[comm->rank];
@@ -94,15 +112,28 @@ static ncclResult_t windowRegister(ncclComm* comm, void* buff, size_t size, nccl
     NCCLCHECK(ipcServerStart(comm));
     NCCLCHECK(ipcExport(comm, (void*)base, allocSize, &me.desc));
   }
+  // The handle before the exchange, its outcome in it: a rank without one fails every rank together, in one process
+  // (where no outcome round follows) as across processes.
+  ncclWindow_vidmem* w = nullptr;
+  // (tests: NCCL_AMD_TEST_WIN_HANDLE_FAIL=<rank> makes that rank's handle allocation fail)
+  ncclResult_t mapRes = paramInt("NCCL_AMD_TEST_WIN_HANDLE_FAIL", -1) == comm->rank ? ncclUnhandledCudaError
+                                                                                    : windowAlloc(&w);
+  me.noHandle = mapRes != ncclSuccess;
   ncclResult_t gres = commAllGather(comm, all.data(), sizeof(WinInfo));
+  for (int r = 0; r < comm->nRanks && gres == ncclSuccess; r++)
+    if (all[r].noHandle) {
+      if (r != comm->rank) WARN("ncclCommWindowRegister: rank %d could not allocate its window handle", r);
+      gres = mapRes != ncclSuccess ? mapRes : ncclRemoteError;
+    }
   if (gres != ncclSuccess) {
     if (needIpc) ipcUnexport(comm, me.desc);
+    if (w) (void)hipHostFree(w);
     return gres;
   }
 
-  ncclWindow_vidmem* w = new ncclWindow_vidmem();
-  ncclResult_t mapRes = ncclSuccess;
   w->comm = comm;
+  w->nRanks = comm->nRanks;
+  w->rank = comm->rank;
   w->userPtr = buff;
   w->size = size;
   w->flags = flags;
@@ -155,7 +186,13 @@ static ncclResult_t windowRegister(ncclComm* comm, void* buff, size_t size, nccl
 static void windowRelease(ncclComm* comm, ncclWindow_vidmem* w) {
   for (int r = 0; r < comm->nRanks; r++)
     if (w->peerBase[r]) ipcUnmap(comm, r, w->peerBase[r]);
-  delete w;
+  (void)hipHostFree(w);
+}
+
+void windowDrop(ncclComm* comm, ncclWindow_vidmem* w) {
+  auto it = std::find(comm->windows.begin(), comm->windows.end(), w);
+  if (it != comm->windows.end()) comm->windows.erase(it);
+  windowRelease(comm, w);
 }
 
 ncclWindow_vidmem* findSymWindow(ncclComm* comm, const void* p, size_t bytes) {
@@ -1093,6 +1130,11 @@ NCCL_EXPORT ncclResult_t ncclCommWindowDeregister(ncclComm_t comm, ncclWindow_t 
   auto it = std::find(comm->windows.begin(), comm->windows.end(), win);
   if (it == comm->windows.end() || win->comm != comm) {
     WARN("ncclCommWindowDeregister: unknown window %p", (void*)win);
+    return ncclInvalidArgument;
+  }
+  if (devCommOwnsWindow(comm, win)) {
+    WARN("ncclCommWindowDeregister: window %p is a DevComm's resource window (ncclDevCommDestroy releases it)",
+         (void*)win);
     return ncclInvalidArgument;
   }
   // collectives enqueued on this window may still run: wait for the device before unmapping peers
