@@ -21,11 +21,12 @@ HOSTSRC  := debug.cc bootstrap.cc ipc.cc transport.cc init.cc group.cc enqueue.c
 HOSTOBJ  := $(HOSTSRC:%.cc=$(BUILD)/%.o)
 DEVSRC   := $(notdir $(wildcard $(SRCDIR)/*.hip))
 DEVOBJ   := $(DEVSRC:%.hip=$(BUILD)/%.o)
-HDRS     := $(wildcard $(SRCDIR)/*.h) include/nccl.h include/nccl_device.h
+HDRS     := $(wildcard $(SRCDIR)/*.h) include/nccl.h include/nccl_device.h include/nccl_device_reduce_copy.h
 
 all: lib oracle numerics-host bootstrap-test tuner-test nccl-perf comm-examples plan-test mapcheck-test xgmi-probe atomicity-probe \
      fp8-probe release-probe reuse-probe export-check-test barrier-probe bcast-plan-test bcast-example p2p-plan-test sendrecv-example \
-     rma-plan-test sym-a2a-plan-test comm-split-test devapi-kernels devapi-layout-test devapi-example
+     rma-plan-test sym-a2a-plan-test comm-split-test devapi-kernels devapi-layout-test devapi-example \
+     devapi-rc-kernels devapi-rc-host-test devapi-rc-example
 
 .PHONY: export-check-test
 export-check-test: tests/native/export_check_test
@@ -183,7 +184,7 @@ tests/native/sendrecv_example: tests/native/sendrecv_example.cc include/nccl.h $
 # through ctypes by tests/test_gpu_device_api.py; a CPU sweep of the header's pure functions (resource layout, teams,
 # epoch compare), a stand-alone host program under ASan+UBSan; the reference's LSA AllReduce example restated against
 # the C ABI, one pthread per rank (with a timing mode, profiles/README.md).
-DEVAPIHDRS := include/nccl.h include/nccl_device.h
+DEVAPIHDRS := include/nccl.h include/nccl_device.h include/nccl_device_reduce_copy.h
 devapi-kernels: tests/native/libdevapi_kernels.so
 
 tests/native/libdevapi_kernels.so: tests/native/devapi_kernels.hip $(DEVAPIHDRS) $(LIBDIR)/libnccl.so
@@ -203,6 +204,38 @@ tests/native/devapi_example: tests/native/devapi_example.hip $(DEVAPIHDRS) $(LIB
 	  -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
 .PHONY: devapi-kernels devapi-layout-test devapi-example
+
+# The reduce-copy family of the device API (include/nccl_device_reduce_copy.h, DESIGN.md §2.7 "Reduce-copy"): its test
+# kernels (tests/test_gpu_device_rc.py), built with the temporaries kept, so that the gfx950 assembly and the kernels'
+# register / scratch report lie in build/devapi_rc/ (tests/test_device_rc_cpu.py reads both); a CPU sweep of ncclSymPtr
+# and of the plan function, a stand-alone host program under ASan+UBSan; an LSA AllReduce written with the family, one
+# pthread per rank, with devapi_example's timing mode.
+RCBUILD := $(BUILD)/devapi_rc
+devapi-rc-kernels: tests/native/libdevapi_rc_kernels.so
+
+$(RCBUILD)/libdevapi_rc_kernels.so: tests/native/devapi_rc_kernels.hip $(DEVAPIHDRS) $(LIBDIR)/libnccl.so
+	@mkdir -p $(RCBUILD)
+	$(HIPCC) -O3 -std=c++17 -fPIC -shared -fvisibility=hidden --offload-arch=$(ARCH) -fno-gpu-flush-denormals-to-zero \
+	  -ffp-contract=off -Iinclude -Rpass-analysis=kernel-resource-usage -save-temps=obj -o $@ $< -L$(LIBDIR) -lnccl \
+	  -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' 2> $(RCBUILD)/kernels.usage; \
+	  st=$$?; grep -E "warning|error" $(RCBUILD)/kernels.usage >&2; exit $$st
+
+tests/native/libdevapi_rc_kernels.so: $(RCBUILD)/libdevapi_rc_kernels.so
+	cp $< $@
+
+devapi-rc-host-test: tests/native/devapi_rc_host_test
+
+tests/native/devapi_rc_host_test: tests/native/devapi_rc_host_test.cc $(DEVAPIHDRS)
+	$(CXX) -g -O1 -fno-omit-frame-pointer -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude \
+	  -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
+
+devapi-rc-example: tests/native/devapi_rc_example
+
+tests/native/devapi_rc_example: tests/native/devapi_rc_example.hip $(DEVAPIHDRS) $(LIBDIR)/libnccl.so
+	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude -o $@ $< -L$(LIBDIR) -lnccl -lpthread \
+	  -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
+
+.PHONY: devapi-rc-kernels devapi-rc-host-test devapi-rc-example
 
 # CPU test of ncclCommSplit / ncclCommShrink below the GPU: membership and inherited occupancy (split.h), the channel
 # cap they feed (enqueue.cc, its launches stubbed) and the subset rounds and rendezvous of the bootstrap, ranks as threads

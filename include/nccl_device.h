@@ -3,7 +3,7 @@
  *
  * A kernel of the caller's own reads and writes its peers' memory through registered windows and synchronises with
  * the other ranks from inside the kernel. This header restates the public names, struct roles and signatures of the
- * reference's device API (src/include/nccl_device/core.h, coop.h, ptr.h, lsa_barrier.h) for the subset that has a
+ * reference's device API (src/include/nccl_device/core.h, coop.h, ptr.h, lsa_barrier.h, reduce_copy.h) for the subset that has a
  * hardware counterpart on a full-mesh xGMI node: every rank is load/store accessible from every other, so the world
  * team and the LSA team are the same team and the LSA subset is the whole intra-node device API. The implementation
  * is this project's own.
@@ -14,14 +14,19 @@
  *   - kernels are launched with hipLaunchKernelGGL / <<<>>> on a hipStream_t.
  * Nothing else changes: ncclDevComm is passed to kernels by value, ncclWindow_t by value.
  *
- * Not provided (no counterpart here): GIN, multimem, ncclSymPtr, reduce_copy, ncclLLA2A, the hybrid
- * ncclBarrierSession, rail teams, ncclLsaBarrierCreateRequirement, the host overloads of the team functions.
+ * ncclSymPtr<T> (ptr.h) is here; the reduce-copy family (reduce_copy.h: ncclLsaReduceSum, ncclLsaCopy,
+ * ncclLsaReduceSumCopy, their lambda and ncclLocal* forms) is in nccl_device_reduce_copy.h, which this header includes
+ * for hipcc.
+ *
+ * Not provided (no counterpart here): GIN, multimem (ncclSymPtr has no multimemPtr / lsaMultimemPtr member and the
+ * ncclMultimem* / *MultimemCopy functions are not declared, so their use fails at compile time), ncclLLA2A, the hybrid
+ * ncclBarrierSession, rail teams, fp8 reduce-copy.
  *
  * Time: every bounded wait counts ticks of __builtin_amdgcn_s_memrealtime(), a constant 100 MHz clock
  * (1 tick = 10 ns; 20 ms = 2,000,000 ticks). `timeoutCycles` arguments are in these ticks.
  *
- * Host-only translation units (plain C++17) may include this header: they see the types, the team functions and the
- * layout function; the device functions need hipcc.
+ * Host-only translation units (plain C++17) may include this header: they see the types, ncclSymPtr's fields and
+ * arithmetic, the team functions and the layout function; the device functions need hipcc.
  */
 #ifndef NCCL_DEVICE_H_
 #define NCCL_DEVICE_H_
@@ -33,6 +38,8 @@
 #endif
 
 #include <atomic>
+#include <cstddef>
+#include <type_traits>
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -331,6 +338,74 @@ NCCL_HOST_DEVICE_INLINE int ncclTeamRankInDifference(ncclTeam_t parent, ncclTeam
   return first + (subset.nRanks - 1) * step + 1 + (rest - inGaps); /* above the subset */
 }
 
+/* ------------------------------------------------------------------------------------------- ncclSymPtr */
+
+/* A typed pointer into a symmetric window: the window and a byte offset, the same on every rank. Arithmetic counts
+ * elements of T (negative steps included); a - b is the distance in elements; conversion to ncclSymPtr<U> keeps window
+ * and byte offset. Host and device. The device members are the window getters below cast to T*. There is no
+ * multimemPtr / lsaMultimemPtr: multimem has no counterpart here, and leaving them undeclared makes a use fail at
+ * compile time. */
+template <typename T>
+struct ncclSymPtr {
+  using ElementType = T;
+  ncclWindow_t window;
+  size_t offset;
+
+  NCCL_HOST_DEVICE_INLINE constexpr ncclSymPtr(ncclWindow_t window = nullptr, size_t offset = 0)
+      : window(window), offset(offset) {}
+
+  template <typename U>
+  NCCL_HOST_DEVICE_INLINE operator ncclSymPtr<U>() const {
+    return ncclSymPtr<U>(window, offset);
+  }
+
+#define NCCL_SYMPTR_STEP(Int)                                     \
+  NCCL_HOST_DEVICE_INLINE ncclSymPtr<T>& operator+=(Int d) {      \
+    offset += (size_t)d * sizeof(T); /* modular: d may be < 0 */  \
+    return *this;                                                 \
+  }                                                               \
+  NCCL_HOST_DEVICE_INLINE ncclSymPtr<T>& operator-=(Int d) {      \
+    offset -= (size_t)d * sizeof(T);                              \
+    return *this;                                                 \
+  }
+  NCCL_SYMPTR_STEP(int)
+  NCCL_SYMPTR_STEP(unsigned int)
+  NCCL_SYMPTR_STEP(long)
+  NCCL_SYMPTR_STEP(unsigned long)
+  NCCL_SYMPTR_STEP(long long)
+  NCCL_SYMPTR_STEP(unsigned long long)
+#undef NCCL_SYMPTR_STEP
+
+#if defined(__HIPCC__)
+  __device__ __forceinline__ T* localPtr() const;
+  __device__ __forceinline__ T* lsaPtr(int peer) const;
+  __device__ __forceinline__ T* peerPtr(int peer) const;
+  __device__ __forceinline__ T* peerPtr(ncclTeam team, int peer) const;
+#endif
+};
+
+template <typename T, typename Int, typename = std::enable_if_t<std::is_integral<Int>::value>>
+NCCL_HOST_DEVICE_INLINE ncclSymPtr<T> operator+(ncclSymPtr<T> p, Int d) {
+  return p += d;
+}
+template <typename T, typename Int, typename = std::enable_if_t<std::is_integral<Int>::value>>
+NCCL_HOST_DEVICE_INLINE ncclSymPtr<T> operator-(ncclSymPtr<T> p, Int d) {
+  return p -= d;
+}
+template <typename T>
+NCCL_HOST_DEVICE_INLINE ptrdiff_t operator-(ncclSymPtr<T> a, ncclSymPtr<T> b) {
+  return ((ptrdiff_t)a.offset - (ptrdiff_t)b.offset) / (ptrdiff_t)sizeof(T);
+}
+/* (the reference declares these two with a ncclSymPtr return type, a slip: they compare) */
+template <typename T>
+NCCL_HOST_DEVICE_INLINE bool operator==(ncclSymPtr<T> a, ncclSymPtr<T> b) {
+  return a.window == b.window && a.offset == b.offset;
+}
+template <typename T>
+NCCL_HOST_DEVICE_INLINE bool operator!=(ncclSymPtr<T> a, ncclSymPtr<T> b) {
+  return !(a == b);
+}
+
 /* ------------------------------------------------------------------------------------- device functions */
 #if defined(__HIPCC__)
 
@@ -379,6 +454,23 @@ NCCL_DEVICE_INLINE void* ncclGetPeerPointer(ncclWindow_t w, size_t offset, int p
 }
 NCCL_DEVICE_INLINE void* ncclGetPeerPointer(ncclWindow_t w, size_t offset, ncclTeam team, int peer) {
   return w->peerPtr[w->rank + (peer - team.rank) * team.stride] + offset;
+}
+
+template <typename T>
+NCCL_DEVICE_INLINE T* ncclSymPtr<T>::localPtr() const {
+  return (T*)ncclGetLocalPointer(window, offset);
+}
+template <typename T>
+NCCL_DEVICE_INLINE T* ncclSymPtr<T>::lsaPtr(int peer) const {
+  return (T*)ncclGetLsaPointer(window, offset, peer);
+}
+template <typename T>
+NCCL_DEVICE_INLINE T* ncclSymPtr<T>::peerPtr(int peer) const {
+  return (T*)ncclGetPeerPointer(window, offset, peer);
+}
+template <typename T>
+NCCL_DEVICE_INLINE T* ncclSymPtr<T>::peerPtr(ncclTeam team, int peer) const {
+  return (T*)ncclGetPeerPointer(window, offset, team, peer);
 }
 
 /* ---- resource buffers (in ncclDevComm::resourceWindow, through its inlined table) ---- */
@@ -533,5 +625,8 @@ struct ncclLsaBarrierSession {
 };
 
 #endif /* __HIPCC__ */
+
+/* The reduce-copy family. Its plan function is host and device; the rest needs hipcc. */
+#include "nccl_device_reduce_copy.h"
 
 #endif /* NCCL_DEVICE_H_ */
