@@ -1,5 +1,6 @@
 // Test kernels of the device API's reduce-copy family (include/nccl_device_reduce_copy.h), written against the two
-// public headers only (libdevapi_rc_kernels.so, driven through ctypes by tests/test_gpu_device_rc.py). Every launcher
+// public headers only (libdevapi_rc_kernels.so, driven through ctypes by tests/test_gpu_device_rc.py and
+// tests/test_gpu_device_rc_edge.py). Every launcher
 // enqueues one kernel on `stream` and returns the launch's hipError_t (or -1 for a code it does not know); the caller
 // guarantees that pointers, offsets and counts lie inside the buffers it passes.
 #include <hip/hip_bf16.h>
@@ -110,29 +111,54 @@ DEVAPI int rc_local(int type, int coop, int wideCount, int form, void* const* sr
   return -1;
 }
 
-// ---- a user RedOp: ncclLsaReduceLsaCopy with max, sources and destinations from pointer tables, one CTA
+// ---- user RedOps: ncclLsaReduceLsaCopy, sources and destinations from pointer tables, one CTA. OpMax is a select;
+// OpUserSum is a + b in T and is not nccl::utility::OpSum, so __half and __hip_bfloat16 fold in T, rounding every step.
 template <typename T>
 struct OpMax {
   using EltType = T;
   __device__ T operator()(T const& a, T const& b) const { return a < b ? b : a; }
 };
 template <typename T>
-__global__ void __launch_bounds__(256) rcMaxKernel(T* const* srcTable, int nSrc, T* const* dstTable, int nDst,
-                                                   size_t count) {
+struct OpUserSum {
+  using EltType = T;
+  __device__ T operator()(T const& a, T const& b) const { return a + b; }
+};
+template <typename T, typename RedOp>
+__global__ void __launch_bounds__(256) rcUserOpKernel(T* const* srcTable, int nSrc, T* const* dstTable, int nDst,
+                                                      size_t count) {
   ncclLsaReduceLsaCopy<T>(ncclCoopCta(), [=](int i) -> T* { return srcTable[i]; }, nSrc,
-                          [=](int i) -> T* { return dstTable[i]; }, nDst, OpMax<T>{}, count);
+                          [=](int i) -> T* { return dstTable[i]; }, nDst, RedOp{}, count);
 }
+template <typename T, typename RedOp>
+static int launchUserOp(void* const* srcTable, int nSrc, void* const* dstTable, int nDst, size_t count,
+                        hipStream_t stream) {
+  hipLaunchKernelGGL((rcUserOpKernel<T, RedOp>), dim3(1), dim3(256), 0, stream, (T* const*)srcTable, nSrc,
+                     (T* const*)dstTable, nDst, count);
+  return (int)hipGetLastError();
+}
+// type: 2 int32, 6 float, 7 double, 8 __half, 9 __hip_bfloat16
 DEVAPI int rc_max(int type, void* const* srcTable, int nSrc, void* const* dstTable, int nDst, size_t count,
                   hipStream_t stream) {
-  if (type == 2)
-    hipLaunchKernelGGL(rcMaxKernel<int32_t>, dim3(1), dim3(256), 0, stream, (int32_t* const*)srcTable, nSrc,
-                       (int32_t* const*)dstTable, nDst, count);
-  else if (type == 6)
-    hipLaunchKernelGGL(rcMaxKernel<float>, dim3(1), dim3(256), 0, stream, (float* const*)srcTable, nSrc,
-                       (float* const*)dstTable, nDst, count);
-  else
-    return -1;
-  return (int)hipGetLastError();
+  switch (type) {
+    case 2: return launchUserOp<int32_t, OpMax<int32_t>>(srcTable, nSrc, dstTable, nDst, count, stream);
+    case 6: return launchUserOp<float, OpMax<float>>(srcTable, nSrc, dstTable, nDst, count, stream);
+    case 7: return launchUserOp<double, OpMax<double>>(srcTable, nSrc, dstTable, nDst, count, stream);
+    case 8: return launchUserOp<__half, OpMax<__half>>(srcTable, nSrc, dstTable, nDst, count, stream);
+    case 9: return launchUserOp<__hip_bfloat16, OpMax<__hip_bfloat16>>(srcTable, nSrc, dstTable, nDst, count, stream);
+  }
+  return -1;
+}
+// type: 6 float, 7 double, 8 __half, 9 __hip_bfloat16
+DEVAPI int rc_usersum(int type, void* const* srcTable, int nSrc, void* const* dstTable, int nDst, size_t count,
+                      hipStream_t stream) {
+  switch (type) {
+    case 6: return launchUserOp<float, OpUserSum<float>>(srcTable, nSrc, dstTable, nDst, count, stream);
+    case 7: return launchUserOp<double, OpUserSum<double>>(srcTable, nSrc, dstTable, nDst, count, stream);
+    case 8: return launchUserOp<__half, OpUserSum<__half>>(srcTable, nSrc, dstTable, nDst, count, stream);
+    case 9:
+      return launchUserOp<__hip_bfloat16, OpUserSum<__hip_bfloat16>>(srcTable, nSrc, dstTable, nDst, count, stream);
+  }
+  return -1;
 }
 
 // ---- LSA forms across ranks. One kernel per case: acquire-sync, the call under test on this CTA's contiguous slice,

@@ -1,7 +1,9 @@
 """CPU tests of the device API's reduce-copy addition (include/nccl_device.h ncclSymPtr,
 include/nccl_device_reduce_copy.h): the stand-alone host sweep of ncclSymPtr and of the plan function (built under
 ASan+UBSan), the gfx950 code of the test kernels (16-byte accesses in the float ncclLsaReduceSumCopy kernel, no scratch
-and no spill in any kernel), and the header as a host-only C++17 translation unit."""
+and no spill in any kernel), the edge-value input sets and numpy reference of tests/test_gpu_device_rc_edge.py (NaN
+cap, one-NaN results, and that the sets tell a wrong fold from the right one), and the header as a host-only C++17
+translation unit."""
 import os
 import re
 import subprocess
@@ -55,6 +57,64 @@ def test_no_kernel_uses_scratch_or_spills(built):
         assert len(vals) == len(names), f
         bad = [(n, v) for n, v in zip(names, vals) if v]
         assert not bad, f"{f}: {bad[:10]}"
+
+
+def test_edge_sets_discriminate(built):
+    """The inputs and the reference of tests/test_gpu_device_rc_edge.py, without a GPU: every set's reference result
+    stays under the NaN cap at every nSrc; an element with exactly one NaN among its sources (and none made by the
+    fold) results in that input's bits; and the sets tell a wrong fold from the right one — on `dr` a fold that rounds
+    per step differs from the fp32 fold on at least 40 % of the non-NaN elements, on `order` the fold with the last two
+    sources exchanged on at least 10 %, on `many` the reversed fold on at least 1 % at every nSrc."""
+    import numpy as np
+    from tests import gpu_cases as G
+    from tests import test_gpu_device_rc_edge as E
+    for kind in E.KINDS:
+        sets = E.edge_sets(kind)
+        assert set(sets) == ({"edge", "many"} | ({"dr", "dr1", "order", "many17"} if kind in E.SHORT else set()))
+        for name, (srcs, nsrcs) in sets.items():
+            ref = E.ref_sum(kind, srcs, nsrcs)
+            for nsrc in nsrcs:
+                want, one = ref[nsrc]
+                share = E.nan_share(kind, want)
+                exact = float((~np.isnan(E.up(kind, want)) | one).mean())
+                print(f"[{kind} {name} nSrc={nsrc}] NaN share {100 * share:.2f} %, compared bit for bit "
+                      f"{100 * exact:.2f} %")
+                assert share <= E.NAN_CAP and G.nan_cap_ok(want, E.KINDS[kind]), (kind, name, nsrc, share)
+                assert one.any() or name not in ("edge", "many", "many17")
+                nans = np.stack([np.isnan(E.up(kind, s)) for s in srcs[:nsrc]])
+                theirs = np.stack([G._raw(s) for s in srcs[:nsrc]])[nans.argmax(0), np.arange(want.size)]
+                assert np.array_equal(G._raw(want)[one], theirs[one]), (kind, name, nsrc)
+            if name in ("edge", "dr", "dr1", "order"):
+                for op in ("sum", "max"):
+                    want, one = E.ref_fold_T(kind, srcs, op)
+                    assert E.nan_share(kind, want) <= E.NAN_CAP, (kind, name, op)
+                    if op == "sum":
+                        nans = np.stack([np.isnan(E.up(kind, s)) for s in srcs])
+                        theirs = np.stack([G._raw(s) for s in srcs])[nans.argmax(0), np.arange(want.size)]
+                        assert np.array_equal(G._raw(want)[one], theirs[one]), (kind, name, op)
+        many = sets["many"][0]
+        for nsrc in E.MANY_NSRC:
+            fwd = E.ref_sum(kind, many[:nsrc])[nsrc][0]
+            rev = E.ref_sum(kind, many[:nsrc][::-1])[nsrc][0]
+            share = E.differing_share(kind, fwd, rev)
+            print(f"[{kind} many nSrc={nsrc}] the reversed fold differs on {100 * share:.1f} %")
+            assert share >= 0.01, (kind, nsrc, share)
+        if kind not in E.SHORT:
+            continue
+        for name in ("dr", "dr1"):
+            srcs = sets[name][0]
+            share = E.differing_share(kind, E.ref_fold_T(kind, srcs, "sum")[0], E.ref_sum(kind, srcs)[3][0])
+            print(f"[{kind} {name}] the per-step fold in T differs from the fp32 fold on {100 * share:.1f} %")
+            assert name != "dr" or share >= 0.40, (kind, name, share)
+        a, swapped, nega = sets["order"][0]
+        share = E.differing_share(kind, E.ref_sum(kind, [a, nega, swapped])[3][0],
+                                  E.ref_sum(kind, [a, swapped, nega])[3][0])
+        print(f"[{kind} order] [a, -a, swapped] differs from [a, swapped, -a] on {100 * share:.1f} %")
+        assert share >= 0.10, (kind, share)
+    # the reference's bf16 rounding on its own: ties to even, a carry into the exponent, overflow to Inf, a quiet NaN
+    f = np.array([0x3f808000, 0x3f818000, 0x3f7f8000, 0x7f7f8000, 0x7f800001, 0xffc12345, 0x00008000, 0x00018000],
+                 dtype=np.uint32).view(np.float32)
+    assert E.down("bfloat16", f).tolist() == [0x3f80, 0x3f82, 0x3f80, 0x7f80, 0x7fc0, 0xffc1, 0x0000, 0x0002]
 
 
 def test_header_compiles_host_only(tmp_path):

@@ -3,7 +3,9 @@ process without a communicator, a user RedOp, the ncclLsa* forms across ranks (i
 as spawned processes), the in-place AllReduce, a child communicator and a captured graph. The kernels are
 tests/native/devapi_rc_kernels.hip (libdevapi_rc_kernels.so, launched through ctypes); expected values come from numpy
 (torch on the CPU for bf16), folded in source order with fp32 accumulation and one final rounding for the 2-byte floats,
-and are compared bit for bit. Every sweep takes its counts from the header's per-round element count P."""
+and are compared bit for bit. Every sweep takes its counts from the header's per-round element count P. The numerics
+of the fold on edge values, NaNs and source order are tests/test_gpu_device_rc_edge.py, which drives lsa_case and
+inplace_case with its own inputs, reference and comparison."""
 import ctypes
 import multiprocessing as mp
 import os
@@ -47,6 +49,7 @@ def _kernels():
         k.rc_round_elts.argtypes, k.rc_round_elts.restype = [S, I], S
         k.rc_local.argtypes = [I, I, I, I, P, P, P, S, P, S, I, I, S, P]
         k.rc_max.argtypes = [I, P, I, P, I, S, P]
+        k.rc_usersum.argtypes = [I, P, I, P, I, S, P]
         k.rc_lsa.argtypes = [I, P, P, S, P, S, S, I, I, I, P]
         _K = k
     return _K
@@ -284,13 +287,15 @@ def _lsa_inputs(kind, count, n, seed):
     return [_values(kind, count, np.random.default_rng(seed * 131 + r)) for r in range(n)]
 
 
-def _lsa_want(kind, xs, n, form, grid):
-    """The payload every rank's receive window must hold after `form`."""
+def _lsa_want(kind, xs, n, form, grid, fold=None):
+    """The payload every rank's receive window must hold after `form`; `fold` (kind, sources) -> their sum replaces
+    _fold for the forms that reduce all ranks."""
     count = xs[0].size
     if form in COPY_FORMS:
         return np.concatenate(xs)
     if form != TWO_TEAM_FORM:
-        return _fold(kind, xs)[n]
+        return fold(kind, xs) if fold else _fold(kind, xs)[n]
+    assert fold is None
     want = np.zeros(count, dtype=xs[0].dtype)
     per = (count + n * grid - 1) // (n * grid)
     for r in range(n):      # part r: the sum over r's run of INNER consecutive ranks
@@ -320,11 +325,27 @@ def _async_errors(rs, what):
     return [f"rank {r.comm.rank} {what}: async error {r.comm.async_error()}" for r in rs if r.comm.async_error()]
 
 
-def lsa_case(rs, n, kind, count, forms, grids, seed, soff=SEND_OFF, roff=RECV_OFF):
-    """Every form x grid on one set of inputs; the ranks `rs` of this process, of n in all. Returns error strings."""
+def _check_window(buf, off, want, what, check=None):
+    """Errors of a window's buffer against the payload `want` at byte `off`, fill everywhere else: bit for bit, or
+    with check(got, want, what) -> errors on the payload's elements and the rest against the fill."""
+    if check is None:
+        return buf.check(_payload(buf.nbytes, off, want), what)
+    raw = buf.store.cpu().numpy()
+    lo, hi = buf.lo + off, buf.lo + off + want.nbytes
+    errs = check(raw[lo:hi].view(want.dtype), want, what)
+    if not (np.all(raw[:lo] == FILL) and np.all(raw[hi:] == FILL)):
+        errs.append(f"{what}: bytes outside the payload were written")
+    return errs
+
+
+def lsa_case(rs, n, kind, count, forms, grids, seed, soff=SEND_OFF, roff=RECV_OFF, inputs=None, fold=None, check=None):
+    """Every form x grid on one set of inputs; the ranks `rs` of this process, of n in all. Returns error strings.
+    inputs: every rank's `count` elements in place of the seeded ones, with fold (kind, sources) -> the expected sum and
+    check (got, want, what) -> errors in place of _fold and the bit-for-bit comparison."""
     torch = _torch()
     code, _ = TYPES[kind]
-    xs = _lsa_inputs(kind, count, n, seed)
+    xs = _lsa_inputs(kind, count, n, seed) if inputs is None else inputs
+    assert len(xs) == n and all(x.size == count for x in xs)
     for r in rs:
         _fill(r.send, soff, xs[r.comm.rank])
     errs = []
@@ -338,9 +359,9 @@ def lsa_case(rs, n, kind, count, forms, grids, seed, soff=SEND_OFF, roff=RECV_OF
             _launch(rs, code, "swin", soff, "rwin", roff, count, form, grid)
             what = f"{kind} n={n} count={count} form={form} grid={grid} offsets=({soff},{roff})"
             errs += _async_errors(rs, what)
-            want = _lsa_want(kind, xs, n, form, grid)
+            want = _lsa_want(kind, xs, n, form, grid, fold)
             for r in rs:
-                errs += r.recv.check(_payload(r.recv.nbytes, roff, want), f"rank {r.comm.rank} {what}")
+                errs += _check_window(r.recv, roff, want, f"rank {r.comm.rank} {what}", check)
             if errs:
                 return errs
     for r in rs:
@@ -348,13 +369,15 @@ def lsa_case(rs, n, kind, count, forms, grids, seed, soff=SEND_OFF, roff=RECV_OF
     return errs
 
 
-def inplace_case(rs, n, kind, count, grid, seed):
-    """ncclLsaReduceSumCopy with the send window as source and destination, at one offset."""
+def inplace_case(rs, n, kind, count, grid, seed, forms=(10, 13), inputs=None, fold=None, check=None):
+    """ncclLsaReduceSumCopy with the send window as source and destination, at one offset; inputs, fold and check as
+    in lsa_case."""
     torch = _torch()
     code, _ = TYPES[kind]
-    xs = _lsa_inputs(kind, count, n, seed)
+    xs = _lsa_inputs(kind, count, n, seed) if inputs is None else inputs
+    assert len(xs) == n and all(x.size == count for x in xs)
     errs = []
-    for form in (10, 13):
+    for form in forms:
         for r in rs:
             _fill(r.send, SEND_OFF, xs[r.comm.rank])
             r.recv.view.fill_(FILL)
@@ -362,9 +385,9 @@ def inplace_case(rs, n, kind, count, grid, seed):
         _launch(rs, code, "swin", SEND_OFF, "swin", SEND_OFF, count, form, grid)
         what = f"in place {kind} n={n} count={count} form={form} grid={grid}"
         errs += _async_errors(rs, what)
-        want = _fold(kind, xs)[n]
+        want = fold(kind, xs) if fold else _fold(kind, xs)[n]
         for r in rs:
-            errs += r.send.check(_payload(r.send.nbytes, SEND_OFF, want), f"rank {r.comm.rank} {what}")
+            errs += _check_window(r.send, SEND_OFF, want, f"rank {r.comm.rank} {what}", check)
             errs += r.recv.check(np.full(r.recv.nbytes, FILL, dtype=np.uint8), f"rank {r.comm.rank} {what}: recv window")
     return errs
 
