@@ -6,6 +6,11 @@
 //   plan_test NRANKS FUNC(ar|rs|ag|reduce) DTYPE COUNT [ALIGN_OFFSET_BYTES] [CHANCAP]
 // prints one line: algo=<copy|onerank|direct|oneshot|ll|ring|chain> nch=<channels> part=<elements|payloads>
 //                  slice=<elements> steps=<n> chunk=<elements> (ring / chain also: kind= cbdlo= cbdhi=)
+//   plan_test NRANKS many FUNC:DTYPE:COUNT[:ROOT] ...
+// the same line for every op in turn, each planned alone on one communicator ("error=<ncclResult_t>" where planning fails)
+//   PLAN_GEOMETRY=1 (both forms above): the communicator's shape as init.cc commDefaults reads it from the environment
+//   (NCCL_MAX_CTAS / NCCL_MAX_NCHANNELS below CHANCAP, NCCL_MIN_CTAS, NCCL_AMD_NSLOTS, and the slot size from
+//   NCCL_AMD_STAGING_MIB, NCCL_BUFFSIZE and NCCL_AMD_SLOT_BYTES); PLAN_WINDOW=1: every buffer lies in a symmetric window
 //   plan_test NRANKS batch FUNC:DTYPE:COUNT[:OP] ...
 // plans the ops as one group (enqueue.cc planColl / batchable / launchBatch, in group.cc's order) and prints one
 // line per launch: algo=<...> ops=<ops in the launch> grid=<workgroups> ranges=<chOff+nch per op, comma-separated>
@@ -192,6 +197,30 @@ static void initComm(ncclComm& comm, int n, int rank, int chanCap) {
   // PLAN_MULTIPROCESS=1: the peers live in other processes, every one serving registrations (init.cc)
   comm.multiProcess = comm.regIpcAll = getenv("PLAN_MULTIPROCESS") && atoi(getenv("PLAN_MULTIPROCESS"));
   resolveLinkChannels(&comm.tune, n, getenv("NCCL_MAX_CTAS") != nullptr);
+}
+
+// PLAN_GEOMETRY=1: what commDefaults (init.cc) takes from the environment for the communicator's shape, so that a plan
+// printed here is the plan of a communicator created under the same variables
+static void envGeometry(ncclComm& comm, int n) {
+  if (getenv("PLAN_WINDOW") && atoi(getenv("PLAN_WINDOW"))) setWindow(comm, true);
+  if (!getenv("PLAN_GEOMETRY") || !atoi(getenv("PLAN_GEOMETRY"))) return;
+  auto envInt = [](const char* name, int64_t dflt) -> int64_t {
+    const char* v = getenv(name);
+    return v && *v ? strtoll(v, nullptr, 0) : dflt;
+  };
+  comm.minCTAs = (int)envInt("NCCL_MIN_CTAS", envInt("NCCL_MIN_NCHANNELS", 1));
+  comm.maxCTAs = (int)envInt("NCCL_MAX_CTAS", envInt("NCCL_MAX_NCHANNELS", 256));
+  comm.maxCTAs = std::max(1, std::min(comm.maxCTAs, NCCL_AMD_MAX_CHANNELS));
+  comm.minCTAs = std::max(1, std::min(comm.minCTAs, comm.maxCTAs));
+  comm.maxChannels = comm.maxCTAs;
+  comm.chanCap = std::min(comm.chanCap, comm.maxChannels);
+  resolveLinkChannels(&comm.tune, n, getenv("NCCL_MAX_CTAS") != nullptr || getenv("NCCL_MAX_NCHANNELS") != nullptr);
+  comm.nSlots = std::max<int>(1, (int)envInt("NCCL_AMD_NSLOTS", 2));
+  int64_t sb = (envInt("NCCL_AMD_STAGING_MIB", 1024) << 20) / ((int64_t)comm.maxChannels * 2 * comm.nSlots * (n > 1 ? n : 2));
+  sb = std::max<int64_t>(16 << 10, std::min<int64_t>(sb, 1 << 20));
+  if (int64_t buff = envInt("NCCL_BUFFSIZE", 0)) sb = buff / comm.nSlots;
+  sb = envInt("NCCL_AMD_SLOT_BYTES", sb);
+  comm.slotBytes = (size_t)std::max<int64_t>(4096, (sb + 4095) / 4096 * 4096);
 }
 
 static CollFunc funcOf(const char* f) {
@@ -591,6 +620,35 @@ static void sweepAll() {
   for (const char* v : kSweepEnv) unsetenv(v);
 }
 
+// one line per plan: what reached launchPlan / launchSymPlan last
+static void printPlan() {
+  if (gStubs.kind == 1) {
+    const SymPlan& s = gStubs.sym;
+    printf("algo=sym nch=%d part=%lu slice=0 steps=1 chunk=%lu symcoll=%d\n", s.nChannels, (unsigned long)s.args.part,
+           (unsigned long)s.args.chunk, s.coll);
+    return;
+  }
+  const char* pipes[] = {"ring", "ring", "ring", "chain", "chain"};
+  const LaunchPlan& p = gStubs.plan;
+  if (p.algo == ALGO_PIPE) {
+    const unsigned sub = p.args.refSub ? p.args.refSub : 1;
+    printf("algo=%s kind=%d nch=%d part=%lu slice=%lu steps=%d chunk=%lu cbdlo=%lu cbdhi=%lu refnch=%d sub=%u\n",
+           pipes[p.pipeKind], p.pipeKind, p.nChannels, (unsigned long)p.args.part, (unsigned long)p.args.slice,
+           p.args.nSteps, (unsigned long)p.args.chunk, (unsigned long)p.args.cbdLo, (unsigned long)p.args.cbdHi,
+           p.nChannels / (int)sub, sub);
+    return;
+  }
+  if (p.algo == ALGO_LL)
+    printf("algo=%s nch=%d part=%lu slice=0 steps=1 chunk=%lu\n", p.ll.ops[0].proto == LLP_LL64 ? "ll128" : "ll",
+           p.nChannels, (unsigned long)p.ll.ops[0].part,
+           (unsigned long)p.ll.ops[0].chunk);
+  else
+    printf("algo=%s nch=%d part=%lu slice=%lu steps=%d chunk=%lu cbdlo=%lu cbdhi=%lu refnch=%d sub=%u\n",
+           kAlgoNames[p.algo], p.nChannels, (unsigned long)p.args.part, (unsigned long)p.args.slice, p.args.nSteps,
+           (unsigned long)p.args.chunk, (unsigned long)p.args.cbdLo, (unsigned long)p.args.cbdHi,
+           p.nChannels / (int)(p.args.refSub ? p.args.refSub : 1), p.args.refSub ? p.args.refSub : 1);
+}
+
 int main(int argc, char** argv) {
   gStubs.onLaunch = dumpLaunchPlan;
   gStubs.onSymLaunch = dumpSymPlan;
@@ -644,18 +702,44 @@ int main(int argc, char** argv) {
     gDump.mode = DUMP_PRINT;
     argc--, argv++;
   }
-  if (argc < 5) {
+  if (argc < 5 && !(argc == 4 && !strcmp(argv[2], "many"))) {
     fprintf(stderr, "usage: plan_test NRANKS FUNC DTYPE COUNT [ALIGN_OFFSET] [CHANCAP]\n");
     return 2;
   }
   const int n = atoi(argv[1]);
   const char* f = argv[2];
-  const bool batch = !strcmp(f, "batch");
+  const bool many = !strcmp(f, "many");
+  const bool batch = !strcmp(f, "batch") || many;
   const int dt = batch ? 0 : atoi(argv[3]);
   const size_t count = batch ? 0 : strtoull(argv[4], nullptr, 0);
   const size_t off = !batch && argc > 5 ? strtoull(argv[5], nullptr, 0) : 0;
   ncclComm comm;
   initComm(comm, n, 0, !batch && argc > 6 ? atoi(argv[6]) : 256);
+  envGeometry(comm, n);
+  if (many) {
+    for (int i = 3; i < argc; i++) {
+      char fn[16] = {};
+      int dtype = 7, root = 0;
+      unsigned long long cnt = 0;
+      if (sscanf(argv[i], "%15[^:]:%d:%llu:%d", fn, &dtype, &cnt, &root) < 3) return 2;
+      CollInfo info;
+      memset(&info, 0, sizeof(info));
+      info.func = funcOf(fn);
+      info.opName = argv[i];
+      info.sendbuff = (const void*)0x10000000ull;
+      info.recvbuff = (void*)0x20000000ull;
+      info.count = cnt;
+      info.datatype = (ncclDataType_t)dtype;
+      info.op = ncclSum;
+      info.root = root;
+      info.comm = &comm;
+      gStubs.kind = -1;
+      const ncclResult_t r = launchColl(info);
+      if (r != ncclSuccess) printf("error=%d\n", (int)r);
+      else printPlan();
+    }
+    return 0;
+  }
   if (batch) {
     if (!dump) gStubs.onLaunch = printBatchLaunch;
     bool badSpec = false;
@@ -683,30 +767,6 @@ int main(int argc, char** argv) {
     printf("error=%d\n", (int)r);
     return 1;
   }
-  if (gStubs.kind == 1) {
-    const SymPlan& s = gStubs.sym;
-    printf("algo=sym nch=%d part=%lu slice=0 steps=1 chunk=%lu\n", s.nChannels, (unsigned long)s.args.part,
-           (unsigned long)s.args.chunk);
-    return 0;
-  }
-  const char* pipes[] = {"ring", "ring", "ring", "chain", "chain"};
-  const LaunchPlan& p = gStubs.plan;
-  if (p.algo == ALGO_PIPE) {
-    const unsigned sub = p.args.refSub ? p.args.refSub : 1;
-    printf("algo=%s kind=%d nch=%d part=%lu slice=%lu steps=%d chunk=%lu cbdlo=%lu cbdhi=%lu refnch=%d sub=%u\n",
-           pipes[p.pipeKind], p.pipeKind, p.nChannels, (unsigned long)p.args.part, (unsigned long)p.args.slice,
-           p.args.nSteps, (unsigned long)p.args.chunk, (unsigned long)p.args.cbdLo, (unsigned long)p.args.cbdHi,
-           p.nChannels / (int)sub, sub);
-    return 0;
-  }
-  if (p.algo == ALGO_LL)
-    printf("algo=%s nch=%d part=%lu slice=0 steps=1 chunk=%lu\n", p.ll.ops[0].proto == LLP_LL64 ? "ll128" : "ll",
-           p.nChannels, (unsigned long)p.ll.ops[0].part,
-           (unsigned long)p.ll.ops[0].chunk);
-  else
-    printf("algo=%s nch=%d part=%lu slice=%lu steps=%d chunk=%lu cbdlo=%lu cbdhi=%lu refnch=%d sub=%u\n",
-           kAlgoNames[p.algo], p.nChannels, (unsigned long)p.args.part, (unsigned long)p.args.slice, p.args.nSteps,
-           (unsigned long)p.args.chunk, (unsigned long)p.args.cbdLo, (unsigned long)p.args.cbdHi,
-           p.nChannels / (int)(p.args.refSub ? p.args.refSub : 1), p.args.refSub ? p.args.refSub : 1);
+  printPlan();
   return 0;
 }
