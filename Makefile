@@ -21,12 +21,14 @@ HOSTSRC  := debug.cc bootstrap.cc ipc.cc transport.cc init.cc group.cc enqueue.c
 HOSTOBJ  := $(HOSTSRC:%.cc=$(BUILD)/%.o)
 DEVSRC   := $(notdir $(wildcard $(SRCDIR)/*.hip))
 DEVOBJ   := $(DEVSRC:%.hip=$(BUILD)/%.o)
-HDRS     := $(wildcard $(SRCDIR)/*.h) include/nccl.h include/nccl_device.h include/nccl_device_reduce_copy.h
+HDRS     := $(wildcard $(SRCDIR)/*.h) include/nccl.h include/nccl_device.h include/nccl_device_reduce_copy.h \
+            include/nccl_device_ll_a2a.h
 
 all: lib oracle numerics-host bootstrap-test tuner-test nccl-perf comm-examples plan-test mapcheck-test xgmi-probe atomicity-probe \
      fp8-probe release-probe reuse-probe export-check-test barrier-probe bcast-plan-test bcast-example p2p-plan-test sendrecv-example \
      rma-plan-test sym-a2a-plan-test comm-split-test devapi-kernels devapi-layout-test devapi-example \
-     devapi-rc-kernels devapi-rc-host-test devapi-rc-example
+     devapi-rc-kernels devapi-rc-host-test devapi-rc-example devapi-lla2a-kernels devapi-lla2a-host-test \
+     devapi-lla2a-example
 
 .PHONY: export-check-test
 export-check-test: tests/native/export_check_test
@@ -184,7 +186,7 @@ tests/native/sendrecv_example: tests/native/sendrecv_example.cc include/nccl.h $
 # through ctypes by tests/test_gpu_device_api.py; a CPU sweep of the header's pure functions (resource layout, teams,
 # epoch compare), a stand-alone host program under ASan+UBSan; the reference's LSA AllReduce example restated against
 # the C ABI, one pthread per rank (with a timing mode, profiles/README.md).
-DEVAPIHDRS := include/nccl.h include/nccl_device.h include/nccl_device_reduce_copy.h
+DEVAPIHDRS := include/nccl.h include/nccl_device.h include/nccl_device_reduce_copy.h include/nccl_device_ll_a2a.h
 devapi-kernels: tests/native/libdevapi_kernels.so
 
 tests/native/libdevapi_kernels.so: tests/native/devapi_kernels.hip $(DEVAPIHDRS) $(LIBDIR)/libnccl.so
@@ -236,6 +238,40 @@ tests/native/devapi_rc_example: tests/native/devapi_rc_example.hip $(DEVAPIHDRS)
 	  -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
 .PHONY: devapi-rc-kernels devapi-rc-host-test devapi-rc-example
+
+# ncclLLA2ASession, the low-latency all-to-all of the device API (include/nccl_device_ll_a2a.h, DESIGN.md §2.7 "LLA2A"):
+# its test kernels (tests/test_gpu_device_lla2a.py), whose register / scratch report goes to
+# build/devapi_lla2a/kernels.usage; a CPU sweep of the requirement, slot and epoch functions, a stand-alone host program
+# under ASan+UBSan; a fused small AllReduce in one kernel, one pthread per rank, with devapi_example's timing mode.
+# -packed-fp32-ops (a device target feature; the host pass notes that it does not know it): the fold lambdas of these
+# callers add neighbouring floats, and the compiler may not fuse such adds into packed fp32 instructions. Today's
+# kernels come out the same with and without it.
+LLBUILD := $(BUILD)/devapi_lla2a
+LLFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fno-gpu-flush-denormals-to-zero -ffp-contract=off \
+           -Xclang -target-feature -Xclang -packed-fp32-ops -Iinclude
+devapi-lla2a-kernels: tests/native/libdevapi_lla2a_kernels.so
+
+$(LLBUILD)/libdevapi_lla2a_kernels.so: tests/native/devapi_lla2a_kernels.hip $(DEVAPIHDRS) $(LIBDIR)/libnccl.so
+	@mkdir -p $(LLBUILD)
+	$(HIPCC) $(LLFLAGS) -fPIC -shared -fvisibility=hidden -Rpass-analysis=kernel-resource-usage -o $@ $< -L$(LIBDIR) -lnccl \
+	  -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' 2> $(LLBUILD)/kernels.usage; \
+	  st=$$?; grep -E "warning|error" $(LLBUILD)/kernels.usage >&2; exit $$st
+
+tests/native/libdevapi_lla2a_kernels.so: $(LLBUILD)/libdevapi_lla2a_kernels.so
+	cp $< $@
+
+devapi-lla2a-host-test: tests/native/devapi_lla2a_host_test
+
+tests/native/devapi_lla2a_host_test: tests/native/devapi_lla2a_host_test.cc $(DEVAPIHDRS)
+	$(CXX) -g -O1 -fno-omit-frame-pointer -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude \
+	  -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
+
+devapi-lla2a-example: tests/native/devapi_lla2a_example
+
+tests/native/devapi_lla2a_example: tests/native/devapi_lla2a_example.hip $(DEVAPIHDRS) $(LIBDIR)/libnccl.so
+	$(HIPCC) $(LLFLAGS) -o $@ $< -L$(LIBDIR) -lnccl -lpthread -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
+
+.PHONY: devapi-lla2a-kernels devapi-lla2a-host-test devapi-lla2a-example
 
 # CPU test of ncclCommSplit / ncclCommShrink below the GPU: membership and inherited occupancy (split.h), the channel
 # cap they feed (enqueue.cc, its launches stubbed) and the subset rounds and rendezvous of the bootstrap, ranks as threads

@@ -16,10 +16,12 @@
  *
  * ncclSymPtr<T> (ptr.h) is here; the reduce-copy family (reduce_copy.h: ncclLsaReduceSum, ncclLsaCopy,
  * ncclLsaReduceSumCopy, their lambda and ncclLocal* forms) is in nccl_device_reduce_copy.h, which this header includes
- * for hipcc.
+ * for hipcc. ncclLLA2ASession (ll_a2a.h), the low-latency all-to-all of small values inside a running kernel, is in
+ * nccl_device_ll_a2a.h, included likewise; its buffer is asked for through the resource requirement list
+ * (ncclLLA2ACreateRequirement), not through ncclDevCommRequirements::lsaLLA2ABlockCount / lsaLLA2ASlotCount.
  *
  * Not provided (no counterpart here): GIN, multimem (ncclSymPtr has no multimemPtr / lsaMultimemPtr member and the
- * ncclMultimem* / *MultimemCopy functions are not declared, so their use fails at compile time), ncclLLA2A, the hybrid
+ * ncclMultimem* / *MultimemCopy functions are not declared, so their use fails at compile time), the hybrid
  * ncclBarrierSession, rail teams, fp8 reduce-copy.
  *
  * Time: every bounded wait counts ticks of __builtin_amdgcn_s_memrealtime(), a constant 100 MHz clock
@@ -102,9 +104,10 @@ struct ncclDevResourceRequirements {
 
 /* Same field order and types as the reference's, so a caller's initialised struct is read correctly. Honoured:
  * resourceRequirementsList, lsaBarrierCount. Refused with ncclInvalidUsage when set: teamRequirementsList,
- * lsaMultimem, barrierCount, railGinBarrierCount, lsaLLA2ABlockCount / lsaLLA2ASlotCount, ginForceEnable,
- * ginSignalCount, ginCounterCount, a ginConnectionType other than NONE, worldGinBarrierCount. The remaining gin
- * fields are hints without a meaning here and are ignored. */
+ * lsaMultimem, barrierCount, railGinBarrierCount, lsaLLA2ABlockCount / lsaLLA2ASlotCount (an LLA2A buffer comes through
+ * resourceRequirementsList: ncclLLA2ACreateRequirement, nccl_device_ll_a2a.h), ginForceEnable, ginSignalCount,
+ * ginCounterCount, a ginConnectionType other than NONE, worldGinBarrierCount. The remaining gin fields are hints
+ * without a meaning here and are ignored. */
 struct ncclDevCommRequirements {
   size_t size;
   unsigned int magic;
@@ -485,6 +488,35 @@ NCCL_DEVICE_INLINE void* ncclGetResourceBufferPeerPointer(ncclDevComm const& com
   return ncclGetResourceBufferLsaPointer(comm, h, ncclTeamRankToLsa(comm, team, peer));
 }
 
+/* ---- bounded spins: what every spinning session of this API (LSA barrier, LLA2A) does on its slow path ---- */
+
+/* The first error a kernel records stays (ncclCommGetAsyncError reports it). */
+NCCL_DEVICE_INLINE void ncclDevRecordError(ncclDevComm const& comm, uint32_t code) {
+  uint32_t expected = 0;
+  __hip_atomic_compare_exchange_strong(comm.errorWord, &expected, code, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+/* The slow path of a spin that started at tick t0, taken every 256 polls: should the spin give up? A timed spin gives
+ * up on the abort word or after timeoutCycles ticks and records nothing; an untimed one on the abort word (recording
+ * NCCL_DEVICE_ERR_ABORT), on an error already recorded, and after the communicator's spin timeout (recording
+ * NCCL_DEVICE_ERR_TIMEOUT). */
+NCCL_DEVICE_INLINE bool ncclDevSpinGiveUp(ncclDevComm const& comm, uint64_t t0, bool timed, uint64_t timeoutCycles) {
+  const uint64_t waited = __builtin_amdgcn_s_memrealtime() - t0;
+  const bool aborted = __hip_atomic_load(comm.abortFlag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0;
+  if (timed) return aborted || waited > timeoutCycles;
+  if (aborted) {
+    ncclDevRecordError(comm, NCCL_DEVICE_ERR_ABORT);
+    return true;
+  }
+  if (__hip_atomic_load(comm.errorWord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) return true;
+  if (waited > comm.timeoutTicks) {
+    ncclDevRecordError(comm, NCCL_DEVICE_ERR_TIMEOUT);
+    return true;
+  }
+  return false;
+}
+
 /* ---- the LSA barrier ----
  *
  * Barrier `index` of a team: every member keeps an epoch (in its own resource memory, so consecutive kernels and
@@ -575,29 +607,6 @@ struct ncclLsaBarrierSession {
 
   static NCCL_DEVICE_INLINE void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
-  NCCL_DEVICE_INLINE void recordError(uint32_t code) const {
-    uint32_t expected = 0;
-    __hip_atomic_compare_exchange_strong(comm_.errorWord, &expected, code, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                         __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-
-  // the slow path of a spin, every 256 polls
-  NCCL_DEVICE_INLINE bool giveUp(uint64_t t0, bool timed, uint64_t timeoutCycles) const {
-    const uint64_t waited = __builtin_amdgcn_s_memrealtime() - t0;
-    const bool aborted = __hip_atomic_load(comm_.abortFlag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0;
-    if (timed) return aborted || waited > timeoutCycles;
-    if (aborted) {
-      recordError(NCCL_DEVICE_ERR_ABORT);
-      return true;
-    }
-    if (__hip_atomic_load(comm_.errorWord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) return true;
-    if (waited > comm_.timeoutTicks) {
-      recordError(NCCL_DEVICE_ERR_TIMEOUT);
-      return true;
-    }
-    return false;
-  }
-
   NCCL_DEVICE_INLINE ncclResult_t waitFor(std::memory_order order, bool timed, uint64_t timeoutCycles) {
     const int nPeers = team_.nRanks - 1;
     const uint32_t want = epoch_ + 1;
@@ -610,7 +619,7 @@ struct ncclLsaBarrierSession {
       while (!ncclLsaEpochReached(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), want)) {
         if (polls == 0) t0 = __builtin_amdgcn_s_memrealtime();
         __builtin_amdgcn_s_sleep(1);
-        if ((++polls & 255) == 0 && giveUp(t0, timed, timeoutCycles)) {
+        if ((++polls & 255) == 0 && ncclDevSpinGiveUp(comm_, t0, timed, timeoutCycles)) {
           gaveUp = true;
           break;
         }
@@ -628,5 +637,8 @@ struct ncclLsaBarrierSession {
 
 /* The reduce-copy family. Its plan function is host and device; the rest needs hipcc. */
 #include "nccl_device_reduce_copy.h"
+
+/* ncclLLA2ASession. Its requirement and slot functions are host and device; the session needs hipcc. */
+#include "nccl_device_ll_a2a.h"
 
 #endif /* NCCL_DEVICE_H_ */

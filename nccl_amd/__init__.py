@@ -236,6 +236,13 @@ class DevComm:
         return self.struct.resourceWindow or 0
 
 
+def lla2a_requirement(n_blocks: int, n_slots: int) -> tuple:
+    """ncclLLA2ACreateRequirement (include/nccl_device_ll_a2a.h) as a (size, align) pair for dev_comm_create's
+    `buffers`: n_blocks blocks of one epoch line and n_slots 16-byte lines per parity. The buffer's entry of
+    DevComm.buffer_handles and n_slots make the kernel's ncclLLA2AHandle."""
+    return n_blocks * (1 + 2 * n_slots) * 16, 16
+
+
 def get_version_code_static() -> int:
     return 2 * 10000 + 30 * 100 + 7  # NCCL_VERSION(2,30,7)
 
