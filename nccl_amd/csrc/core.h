@@ -315,6 +315,10 @@ struct CommTuning {
   // ncclSend / ncclRecv (p2p.cc): bytes per channel part and channels per peer and direction (device_abi.h p2pCut)
   int64_t p2pChunkBytes;    // NCCL_AMD_P2P_CHUNK_BYTES
   int p2pMinCh, p2pMaxCh;   // NCCL_MIN_P2P_NCHANNELS / NCCL_MAX_P2P_NCHANNELS (reference src/channel.cc / init.cc)
+  // ... and their LL protocol (device_abi.h p2pLLCut): off unless p2pLLBytes > 0
+  int64_t p2pLLBytes;       // NCCL_AMD_P2P_LL_BYTES: messages of up to this many bytes take LL lines (0 = off, the default)
+  int64_t p2pLLLineBytes;   // NCCL_AMD_P2P_LL_LINE_BYTES: line bytes per (channel, slot, sender), a multiple of 16
+  int p2pLLNch;             // NCCL_AMD_P2P_LL_NCHANNELS: channels of the line area
   // size table (NCCL_AMD_SIZE_TABLE, enqueue.cc sizeTable): per rank count, the upper ends of the LL, LL128-class
   // and one-shot ranges in bytes (0 = the built-in default); loaded once at init and agreed with rank 0's
   int64_t tableLL[NCCL_AMD_MAX_RANKS + 1], tableLL128[NCCL_AMD_MAX_RANKS + 1], tableOneShot[NCCL_AMD_MAX_RANKS + 1];
@@ -373,6 +377,10 @@ struct ncclComm {
   bool tunerLoaded = false;
   int llChannels = 32;      // LL protocol: channels and line bytes per (channel, parity, sender)
   size_t llBytes = 32 << 10;
+  // LL protocol of ncclSend / ncclRecv: channels of the line area (0: none allocated, every message is staged; lowered
+  // to chanCap / 2 after the allocation, like llChannels) and line bytes per (channel, slot, sender)
+  int p2pLLChannels = 0;
+  size_t p2pLLLineBytes = 0;
   int chanCap = 0;  // channels per launch that stay co-resident even with several ranks per GPU
   // ranks per GPU the cap is computed from: this communicator's own table's, or, for a child of ncclCommSplit /
   // ncclCommShrink, its parent's (copied down every generation)
@@ -605,7 +613,7 @@ struct P2pOp {  // one recorded ncclSend / ncclRecv (AlltoAll / Gather / Scatter
   int peer;
   bool recv;
 };
-struct P2pLaunch {  // one p2pKernel launch: the streams of rounds firstRound .. lastRound
+struct P2pLaunch {  // one p2pKernel / p2pLLKernel launch: the streams of rounds firstRound .. lastRound
   int grid;
   int firstRound, lastRound;
   std::vector<P2pStream> streams;

@@ -30,6 +30,16 @@
 //     observed torn, 64-byte segments are not (tests/native/store_atomicity_probe).
 //     A separate area, so stale LL64 payload can never alias an LL flag position and vice versa.
 //
+//   p2p LL lines (the LL protocol of ncclSend / ncclRecv, at DevComm::p2pLLOffset, after the LL64 area; allocated only
+//     when NCCL_AMD_P2P_LL_BYTES > 0; kernels.h p2pLLKernel)
+//     [channel < p2pLLChannels][slot < kP2pLLDepth][from < nRanks][p2pLLLineBytes]: the same 16-byte lines, written
+//     only by `from`, read only by the owner. The sequence is per ORDERED PAIR and channel, not per channel: LL message
+//     q (0-based; CTR_P2PLL_SEND[c][peer] at the sender, CTR_P2PLL_RECV[c][from] at the receiver) uses slot
+//     q % kP2pLLDepth and the flag (uint32_t)(q + 1) (0 mapped to 1). The receiver stores q + 1 into the sender's
+//     FLG_P2PLL_ACK[c][receiver] once it has placed the message; the sender stores into a slot only once the ack has
+//     reached q + 1 - kP2pLLDepth. A third area, so a stale payload of a collective can never sit where a p2p message
+//     reads a flag, and vice versa.
+//
 //   counters (plain device memory, local)
 //     uint64 [channel][ctr kind < CTR_KINDS (sendRS, recvRS, sendAG, recvAG, sym, ...)][peer < NCCL_AMD_MAX_RANKS]
 //     Per-connection step counters (reference: conn->step, src/device/prims_simple.h:100-173),
@@ -53,15 +63,18 @@ enum StagingKind { STG_RS = 0, STG_AG = 1, STG_KINDS = 2 };
 // rmaWaitKernel), channel 0's rows only: the signal word per sender; signals this rank raised per
 // peer, signals it consumed per peer, and the workgroups of a put launch that finished a message for a peer. Only the
 // one-sided kernels touch these rows: the channel kernels load and store rows below CTR_CHAN_KINDS.
+// FLG_P2PLL_ACK and CTR_P2PLL_SEND / CTR_P2PLL_RECV: the LL protocol of ncclSend / ncclRecv (kernels.h p2pLLKernel):
+// per channel and peer, the LL messages of mine the peer has consumed; the LL messages sent to / received from the peer.
+// Appended after the existing kinds, the counter rows above CTR_CHAN_KINDS: only p2pLLKernel touches them.
 enum FlagKind {
   FLG_RS_READY = 0, FLG_RS_ACK = 1, FLG_AG_READY = 2, FLG_AG_ACK = 3,
   FLG_SYM_ENTER = 4, FLG_SYM_MID = 5, FLG_SYM_DONE = 6, FLG_PULL_READY = 7, FLG_PULL_ACK = 8,
-  FLG_REG_SEND = 9, FLG_REG_RECV = 10, FLG_SIGNAL = 11, FLG_KINDS = 12
+  FLG_REG_SEND = 9, FLG_REG_RECV = 10, FLG_SIGNAL = 11, FLG_P2PLL_ACK = 12, FLG_KINDS = 13
 };
 enum CtrKind {
   CTR_SEND_RS = 0, CTR_RECV_RS = 1, CTR_SEND_AG = 2, CTR_RECV_AG = 3, CTR_SYM = 4, CTR_LL = 5,
   CTR_PULL_PUB = 6, CTR_PULL_GOT = 7, CTR_CHAN_KINDS = 8,  // the rows a channel kernel keeps in LDS (ChanState)
-  CTR_SIG_SENT = 8, CTR_SIG_SEEN = 9, CTR_SIG_ARRIVE = 10, CTR_KINDS = 11
+  CTR_SIG_SENT = 8, CTR_SIG_SEEN = 9, CTR_SIG_ARRIVE = 10, CTR_P2PLL_SEND = 11, CTR_P2PLL_RECV = 12, CTR_KINDS = 13
 };
 
 // Ring / chain kernels (pipe.h; NCCL_ALGO=RING / TREE)
@@ -91,6 +104,10 @@ struct DevComm {
   int llChannels;
   uint32_t* abortFlag;                   // host-pinned; nonzero = abort
   uint32_t* errorWord;                   // host-pinned; first DevError recorded
+  uint64_t p2pLLOffset;                  // p2p LL line area inside every rank's flag allocation (after the LL64 area)
+  uint64_t p2pLLLineBytes;               // line bytes per (channel, slot, sender): 16 per 8 payload bytes
+  int p2pLLChannels;                     // 0: no area (NCCL_AMD_P2P_LL_BYTES unset), every message is staged
+  int p2pLLPad;
 };
 
 // Kernel argument block (passed by value, < 4 KiB like the reference's ncclDevKernelArgs4K,
@@ -210,6 +227,10 @@ __host__ __device__ inline uint64_t llLineOffset(const DevComm& dc, int c, int p
 __host__ __device__ inline uint64_t ll64LineOffset(const DevComm& dc, int c, int parity, int from) {
   return dc.ll64Offset + (((uint64_t)c * 2 + parity) * dc.nRanks + from) * dc.llBytes;
 }
+constexpr int kP2pLLDepth = 4;  // slots per (channel, sender) of the p2p LL line area = LL messages a sender may run ahead
+__host__ __device__ inline uint64_t p2pLLLineOffset(const DevComm& dc, int c, int slot, int from) {
+  return dc.p2pLLOffset + (((uint64_t)c * kP2pLLDepth + slot) * dc.nRanks + from) * dc.p2pLLLineBytes;
+}
 __host__ __device__ inline uint64_t flagIndex(int c, int kind, int from) {
   return ((uint64_t)c * FLG_KINDS + kind) * NCCL_AMD_MAX_RANKS + from;
 }
@@ -260,6 +281,20 @@ __host__ __device__ inline P2pCut p2pCut(uint64_t bytes, uint64_t chunk, int min
   c.nch = (int)((bytes + c.part - 1) / c.part);
   return c;
 }
+// The LL cut of a message (kernels.h p2pLLKernel): units = ceil(bytes / 8) payloads of 8 bytes, perCh = lineBytes / 16 of
+// them per channel and slot, nch = ceil(units / perCh) channel parts of part = ceil(units / nch) UNITS, part j on
+// physical channel j (llPartBounds). From the byte count and rank-0 constants alone, like p2pCut, so both ends agree.
+// nch == 0: not an LL message (empty, or more parts than maxCh channels) — it is staged.
+__host__ __device__ inline P2pCut p2pLLCut(uint64_t bytes, uint64_t lineBytes, int maxCh) {
+  P2pCut c = {0, 0};
+  const uint64_t units = (bytes + 7) / 8, perCh = lineBytes / 16;
+  if (units == 0 || perCh == 0 || maxCh < 1) return c;
+  const uint64_t nch = (units + perCh - 1) / perCh;
+  if (nch > (uint64_t)maxCh) return c;
+  c.nch = (int)nch;
+  c.part = (units + nch - 1) / nch;
+  return c;
+}
 // slices of channel part j: steps, and bytes [lo, hi) of the message at step s (sliceBounds over the whole message)
 __host__ __device__ inline int p2pSteps(uint64_t bytes, uint64_t part, uint64_t slice, int j) {
   uint64_t lo, hi;
@@ -308,13 +343,14 @@ struct SymA2AArgs {
 
 // One message of a stream, and one stream = the in-order messages of one group to (recv == 0) or from one peer.
 // Stream i runs on workgroups wgOff .. wgOff + nch - 1 of its launch, workgroup wgOff + j on physical channel j, which
-// walks the stream's messages in order and skips those cut into j or fewer parts.
+// walks the stream's messages in order and skips those cut into j or fewer parts. An LL message (ll != 0) carries the
+// LL cut: part in 8-byte units, nch <= p2pLLChannels; a stream's nch is the maximum over both kinds.
 struct P2pMsg {
   uint64_t ptr;
   uint64_t bytes;
   uint64_t part;
   uint32_t nch;
-  uint32_t pad;
+  uint32_t ll;  // 0 staged (p2pCut), 1 LL (p2pLLCut)
 };
 struct P2pStream {
   uint16_t wgOff, nch, msgOff, nMsgs;

@@ -258,6 +258,13 @@ void loadTuning(CommTuning* t) {
   if (t->p2pChunkBytes < 16) t->p2pChunkBytes = 16;
   t->p2pMinCh = (int)std::max<int64_t>(1, paramInt("NCCL_MIN_P2P_NCHANNELS", 1));
   t->p2pMaxCh = (int)std::max<int64_t>(1, paramInt("NCCL_MAX_P2P_NCHANNELS", 32));
+  // their LL protocol (kernels.h p2pLLKernel, device_abi.h p2pLLCut): messages of up to NCCL_AMD_P2P_LL_BYTES take
+  // flag-in-data lines. 0 (default): off, and no line area is allocated — no xGMI link has measured where LL stops
+  // paying, the project's practice for such paths (the LL128 class, eager registration). The line
+  // area holds lineBytes / 2 payload bytes per channel, slot and sender on NCHANNELS channels.
+  t->p2pLLBytes = std::max<int64_t>(0, paramInt("NCCL_AMD_P2P_LL_BYTES", 0));
+  t->p2pLLLineBytes = std::max<int64_t>(16, paramInt("NCCL_AMD_P2P_LL_LINE_BYTES", 16384) / 16 * 16);
+  t->p2pLLNch = (int)std::max<int64_t>(1, paramInt("NCCL_AMD_P2P_LL_NCHANNELS", 4));
   // the size table's ranges (per rank count; NCCL_AMD_SIZE_TABLE overrides rows, the three knobs below all rows)
   (void)loadSizeTable(t, paramStr("NCCL_AMD_SIZE_TABLE"));
   t->oneShotBytes = paramInt("NCCL_AMD_ONESHOT_BYTES", 0);  // 0: size table default (2 MiB / nRanks; 2 MiB at 2 ranks)

@@ -20,6 +20,7 @@
 //   symKernel  the zero-copy kernels for buffers in symmetric windows (peers' buffers pulled directly),
 //   symA2AKernel  ncclAlltoAll / ncclGather with the sendbuff in a symmetric window (one pulled copy per byte),
 //   p2pKernel  ncclSend / ncclRecv: one workgroup per (direction, peer, channel) over the pair's RS slots and credits,
+//   p2pLLKernel  ... and their small messages on flag-in-data lines with a per-pair sequence and credit,
 //   rmaPutKernel / rmaWaitKernel  ncclPutSignal / ncclSignal / ncclWaitSignal: stores straight into the peer's window,
 //              one posting wave per peer; one polling wave,
 //   oneRankKernel (PreMulSum at nRanks == 1; the nRanks == 1 copy lives in kernels.hip).
@@ -1275,10 +1276,13 @@ __global__ void __launch_bounds__(kThreads) kCoResident collBatchKernel(CollBatc
 // ncclSend / ncclRecv (and the AlltoAll / Gather / Scatter built from them). One workgroup serves one
 // (direction, peer, channel): it walks that stream's messages in order, each in slices through the pair's own RS
 // slots, credits and flags on that channel — exactly the one-to-one transfer of Channel::bcastA / bcastB, so the
-// pair's sequence stays in step with every other collective. Bytes, whatever the user's datatype; always staged,
-// always pushed (NCCL_AMD_RS_PULL is not applied), no LL path (an LL epoch is a per-channel sequence every rank
-// advances). Several workgroups of one launch share a physical channel (one per direction and peer), so each
-// loads and stores ONLY its own counter word, never the channel's block (loadCounters / storeCounters).
+// pair's sequence stays in step with every other collective. Bytes, whatever the user's datatype; always pushed
+// (NCCL_AMD_RS_PULL is not applied). Small messages can take flag-in-data lines instead (NCCL_AMD_P2P_LL_BYTES): the
+// collectives' LL epoch is a per-channel sequence every rank advances, so p2p LL keeps a sequence, line slots and a
+// credit of its own per ordered pair and channel (p2pLLKernel; it serves the launches that hold an LL message,
+// p2pKernel every other launch, unchanged; both are p2pRun, below the LL helpers). Several workgroups of one launch share a physical channel
+// (one per direction and peer), so each loads and stores ONLY its own counter word, never the channel's block
+// (loadCounters / storeCounters).
 struct P2pShared {
   ChanState st;  // (only `abort`: waitAll's interface)
   uint64_t want[NCCL_AMD_MAX_RANKS];
@@ -1286,67 +1290,13 @@ struct P2pShared {
   uint64_t sigVal[1];
 };
 
+// Which stream of the launch this workgroup serves (streams in workgroup order)
 template <int S, int M>
-__global__ void __launch_bounds__(kThreads) kCoResident p2pKernel(P2pArgs<S, M> a) {
-  __shared__ P2pShared sh;
-  const DevComm& dc = *a.comm;
-  const int tid = threadIdx.x, me = dc.rank, nSlots = dc.nSlots;
+__device__ __forceinline__ int p2pStreamOf(const P2pArgs<S, M>& a) {
   int si = 0;
   for (int i = 1; i < a.nStreams && i < S; i++)
-    if ((int)blockIdx.x >= (int)a.st[i].wgOff) si = i;  // streams in workgroup order
-  const P2pStream sd = a.st[si];
-  const int c = (int)blockIdx.x - (int)sd.wgOff;  // part j runs on physical channel j
-  const int peer = sd.peer;
-  const bool recv = sd.recv != 0;
-  // protoFlags as in runChannel: 1 acquire on credit waits, 2 release on credit signals, 8 no release fence before
-  // data flags, 64 no acquire after data waits
-  const bool forceAcq = (a.protoFlags & 1) != 0, forceRel = (a.protoFlags & 2) != 0, noRel = (a.protoFlags & 8) != 0,
-             noAcq = (a.protoFlags & 64) != 0;
-  if (tid < NCCL_AMD_MAX_RANKS) sh.want[tid] = 0;
-  if (tid == 0) sh.st.abort = 0;
-  // malformed arguments (the host's grid check refuses them first): touch nothing
-  const bool valid = c >= 0 && c < (int)sd.nch && c < dc.maxChannels && peer < dc.nRanks && peer != me;
-  uint64_t* const ctrWord = dc.counters + ctrIndex(valid ? c : 0, recv ? CTR_RECV_RS : CTR_SEND_RS, valid ? peer : 0);
-  uint64_t seq = valid ? *ctrWord : 0;
-  __syncthreads();
-  if (!valid) return;
-  const uint64_t slice = p2pSliceBytes(dc.slotBytes);
-  const uint64_t* myFlags = dc.flags[me] + flagIndex(c, recv ? FLG_RS_READY : FLG_RS_ACK, 0);
-  uint64_t* const peerFlag = dc.flags[peer] + flagIndex(c, recv ? FLG_RS_ACK : FLG_RS_READY, me);
-  bool ok = true;
-  for (int m = 0; ok && m < (int)sd.nMsgs; m++) {
-    const P2pMsg msg = a.msg[(int)sd.msgOff + m];
-    if (c >= (int)msg.nch) continue;
-    char* const user = (char*)msg.ptr;
-    const bool aligned = (msg.ptr & 15) == 0 && !a.elementwise;  // this side's buffer only: staging is always aligned
-    const int nSteps = p2pSteps(msg.bytes, msg.part, slice, c);
-    for (int s = 0; ok && s < nSteps; s++) {
-      uint64_t lo, hi;
-      sliceBounds(msg.part, slice, c, s, msg.bytes, lo, hi);
-      const int slot = (int)(seq % (uint64_t)nSlots);
-      if (tid == 0) {
-        // send: the slot is free once the peer acked slice seq - nSlots; recv: slice seq has arrived
-        sh.want[peer] = recv ? seq + 1 : (seq + 1 > (uint64_t)nSlots ? seq + 1 - nSlots : 0);
-        sh.sigPtr[0] = peerFlag;
-        sh.sigVal[0] = seq + 1;
-      }
-      __syncthreads();
-      if (recv) {
-        ok = waitAll(dc, sh.st, myFlags, sh.want, !noAcq);
-        if (!ok) break;
-        copyRange<uint8_t, false>(user + lo, dc.staging[me] + stagingOffset(dc, c, STG_RS, slot, peer), hi - lo, aligned);
-        signalAll(sh.sigPtr, sh.sigVal, 1, forceRel);  // credit only: the slot's loads have completed
-      } else {
-        ok = waitAll(dc, sh.st, myFlags, sh.want, forceAcq);
-        if (!ok) break;
-        copyRange<uint8_t, true>(dc.staging[peer] + stagingOffset(dc, c, STG_RS, slot, me), user + lo, hi - lo, aligned);
-        signalAll(sh.sigPtr, sh.sigVal, 1, !noRel);
-      }
-      seq++;
-      __syncthreads();
-    }
-  }
-  if (tid == 0) *ctrWord = seq;
+    if ((int)blockIdx.x >= (int)a.st[i].wgOff) si = i;
+  return si;
 }
 
 // ------------------------------------------------------------------------------------ one-sided put / signal / wait
@@ -1909,6 +1859,144 @@ __device__ __forceinline__ void llStore8(char* base, uint64_t pk, uint64_t nbyte
   }
 }
 
+// ------------------------------------------------------------------------------------ point-to-point, LL protocol
+// ncclSend / ncclRecv of small messages (the launches that hold at least one message tagged LL by
+// p2p.cc — every other launch runs p2pKernel). One workgroup per (direction, peer, channel) as there, walking its
+// stream's messages in order: a staged message through the same slice loop, part c of an LL message through the pair's
+// own line slots (device_abi.h "p2p LL lines"). LL message q of the pair-channel uses slot q % kP2pLLDepth and the
+// flag (uint32_t)(q + 1), 0 mapped to 1 as in the collectives' LL.
+//   send: lane 0 waits until the peer has acked message q - kP2pLLDepth (the slot's previous tenant; already true in
+//         steady state), the workgroup barriers, then every lane strides the part's 8-byte units: llLoad8 from the
+//         user buffer (any alignment, ragged tail) and ONE write-through 16-byte store {lo32, flag, hi32, flag} into the
+//         peer's slot. No staging copy, no ready flag, no fence, no drain: the line carries its own flag.
+//   recv: every lane polls its lines until both flag halves show q + 1 (llPollLine: bounded, abort and timeout
+//         reported) and places the payload with llStore8; after a workgroup barrier (every line of the slot has been
+//         read) one lane stores q + 1 into the sender's ack word — a credit, with no release: it publishes nothing.
+// A slot is rewritten only after its ack, and the flag a receiver waits for differs from the slot's previous one
+// (q + 1 - kP2pLLDepth), so a stale line is never taken for a new one. The two sequences (LL messages sent to / received
+// from the peer on this channel) live in the counter rows CTR_P2PLL_SEND / CTR_P2PLL_RECV, beside the staged ones: a
+// workgroup loads and stores only its own two words.
+// The body of both kernels: LL == false is p2pKernel, the staged slice loop alone; LL == true adds the line protocol.
+template <int S, int M, bool LL>
+__device__ __forceinline__ void p2pRun(const P2pArgs<S, M>& a, P2pShared& sh) {
+  const DevComm& dc = *a.comm;
+  const int tid = threadIdx.x, me = dc.rank, nSlots = dc.nSlots;
+  const P2pStream sd = a.st[p2pStreamOf(a)];
+  const int c = (int)blockIdx.x - (int)sd.wgOff;  // part j runs on physical channel j
+  const int peer = sd.peer;
+  const bool recv = sd.recv != 0;
+  // protoFlags as in runChannel: 1 acquire on credit waits, 2 release on credit signals, 8 no release fence before
+  // data flags, 64 no acquire after data waits
+  const bool forceAcq = (a.protoFlags & 1) != 0, forceRel = (a.protoFlags & 2) != 0, noRel = (a.protoFlags & 8) != 0,
+             noAcq = (a.protoFlags & 64) != 0;
+  if (tid < NCCL_AMD_MAX_RANKS) sh.want[tid] = 0;
+  if (tid == 0) sh.st.abort = 0;
+  // malformed arguments (the host's grid check refuses them first): touch nothing
+  const bool valid = c >= 0 && c < (int)sd.nch && c < dc.maxChannels && peer < dc.nRanks && peer != me;
+  uint64_t* const ctrWord = dc.counters + ctrIndex(valid ? c : 0, recv ? CTR_RECV_RS : CTR_SEND_RS, valid ? peer : 0);
+  uint64_t* const llCtrWord = dc.counters + ctrIndex(valid ? c : 0, recv ? CTR_P2PLL_RECV : CTR_P2PLL_SEND, valid ? peer : 0);
+  uint64_t seq = valid ? *ctrWord : 0;
+  uint64_t q = LL && valid ? *llCtrWord : 0;  // LL messages of this pair-channel so far
+  __syncthreads();
+  if (!valid) return;
+  const uint64_t slice = p2pSliceBytes(dc.slotBytes);
+  const uint64_t* myFlags = dc.flags[me] + flagIndex(c, recv ? FLG_RS_READY : FLG_RS_ACK, 0);
+  uint64_t* const peerFlag = dc.flags[peer] + flagIndex(c, recv ? FLG_RS_ACK : FLG_RS_READY, me);
+  bool ok = true;
+  for (int m = 0; ok && m < (int)sd.nMsgs; m++) {
+    const P2pMsg msg = a.msg[(int)sd.msgOff + m];
+    if (c >= (int)msg.nch) continue;
+    char* const user = (char*)msg.ptr;
+    if constexpr (LL) {
+      if (msg.ll) {
+        // (the host tags no message LL beyond the line area's channels or a slot's lines: its grid check refuses them)
+        if (c >= dc.p2pLLChannels || msg.part * 16 > dc.p2pLLLineBytes) break;
+        uint64_t lo, hi;
+        llPartBounds(msg.part, c, (msg.bytes + 7) / 8, lo, hi);
+        const uint32_t flag = (uint32_t)(q + 1) ? (uint32_t)(q + 1) : 1u;
+        // recv: my slot for the peer and the sender's ack word for me; send: the peer's slot for me and my ack word
+        char* const slot = (char*)dc.flags[recv ? me : peer] + p2pLLLineOffset(dc, c, (int)(q % kP2pLLDepth), recv ? peer : me);
+        uint64_t* const ackWord = dc.flags[recv ? peer : me] + flagIndex(c, FLG_P2PLL_ACK, recv ? me : peer);
+        if (!recv) {
+          if (q >= (uint64_t)kP2pLLDepth) {  // the slot had a tenant: message q - kP2pLLDepth, acked as q + 1 - kP2pLLDepth
+            if (tid == 0) {
+              uint64_t t0 = 0;
+              for (uint32_t spins = 0; loadFlag(ackWord) < q + 1 - kP2pLLDepth;) {
+                if (spins == 0) t0 = clockTicks();
+                __builtin_amdgcn_s_sleep(1);
+                if ((++spins & 255) == 0 && spinGiveUp(dc, t0, 0)) {
+                  sh.st.abort = 1;
+                  break;
+                }
+              }
+            }
+            __syncthreads();
+            ok = sh.st.abort == 0;
+          }
+          for (uint64_t i = lo + tid; ok && i < hi; i += kThreads) {
+            const uint64_t v = llLoad8(user, i, msg.bytes);
+            storeRemote(slot + (i - lo) * 16, u32x4{(uint32_t)v, flag, (uint32_t)(v >> 32), flag});
+          }
+        } else {
+          const uint64_t t0 = clockTicks();
+          u32x4 v;
+          for (uint64_t i = lo + tid; ok && i < hi; i += kThreads) {
+            ok = llPollLine(dc, slot + (i - lo) * 16, flag, false, t0, sh.st.abort, v);
+            if (ok) llStore8(user, i, msg.bytes, llPayload(v));  // both halves matched in this one load
+          }
+          __syncthreads();  // every line of the slot has been read: the sender may have it back
+          ok = sh.st.abort == 0;
+          if (ok && tid == 0) storeFlag(ackWord, q + 1);
+        }
+        q++;
+        continue;
+      }
+    }
+    const bool aligned = (msg.ptr & 15) == 0 && !a.elementwise;  // this side's buffer only: staging is always aligned
+    const int nSteps = p2pSteps(msg.bytes, msg.part, slice, c);
+    for (int s = 0; ok && s < nSteps; s++) {
+      uint64_t lo, hi;
+      sliceBounds(msg.part, slice, c, s, msg.bytes, lo, hi);
+      const int slot = (int)(seq % (uint64_t)nSlots);
+      if (tid == 0) {
+        // send: the slot is free once the peer acked slice seq - nSlots; recv: slice seq has arrived
+        sh.want[peer] = recv ? seq + 1 : (seq + 1 > (uint64_t)nSlots ? seq + 1 - nSlots : 0);
+        sh.sigPtr[0] = peerFlag;
+        sh.sigVal[0] = seq + 1;
+      }
+      __syncthreads();
+      if (recv) {
+        ok = waitAll(dc, sh.st, myFlags, sh.want, !noAcq);
+        if (!ok) break;
+        copyRange<uint8_t, false>(user + lo, dc.staging[me] + stagingOffset(dc, c, STG_RS, slot, peer), hi - lo, aligned);
+        signalAll(sh.sigPtr, sh.sigVal, 1, forceRel);  // credit only: the slot's loads have completed
+      } else {
+        ok = waitAll(dc, sh.st, myFlags, sh.want, forceAcq);
+        if (!ok) break;
+        copyRange<uint8_t, true>(dc.staging[peer] + stagingOffset(dc, c, STG_RS, slot, me), user + lo, hi - lo, aligned);
+        signalAll(sh.sigPtr, sh.sigVal, 1, !noRel);
+      }
+      seq++;
+      __syncthreads();
+    }
+  }
+  if (tid == 0) {
+    *ctrWord = seq;
+    if (LL) *llCtrWord = q;
+  }
+}
+
+template <int S, int M>
+__global__ void __launch_bounds__(kThreads) kCoResident p2pKernel(P2pArgs<S, M> a) {
+  __shared__ P2pShared sh;
+  p2pRun<S, M, false>(a, sh);
+}
+template <int S, int M>
+__global__ void __launch_bounds__(kThreads) kCoResident p2pLLKernel(P2pArgs<S, M> a) {
+  __shared__ P2pShared sh;
+  p2pRun<S, M, true>(a, sh);
+}
+
 template <int P>
 __device__ __forceinline__ bool llBcastOp(const DevComm& dc, const LLOp& op, int c, int j, uint64_t e64, int& abortSh) {
   const int tid = threadIdx.x, me = dc.rank, n = dc.nRanks, root = op.root;
@@ -2429,10 +2517,10 @@ inline ncclResult_t launchBcast(const LaunchPlan& p) {
   return ncclSuccess;
 }
 
-// One p2pKernel launch with the smallest argument block that holds it (a template only so that the one unit that
-// calls it, kern_gather.hip, instantiates the kernels)
+// One p2pKernel launch — p2pLLKernel iff the launch holds an LL message — with the smallest argument block that holds
+// it (a template only so that the one unit that calls it, kern_gather.hip, instantiates the kernels)
 template <int S, int M>
-inline void launchP2pArgs(const ncclComm* comm, const P2pLaunch& l, hipStream_t stream) {
+inline void launchP2pArgs(const ncclComm* comm, const P2pLaunch& l, hipStream_t stream, bool ll) {
   P2pArgs<S, M> a;
   __builtin_memset(&a, 0, sizeof(a));
   a.comm = comm->devComm;
@@ -2441,13 +2529,17 @@ inline void launchP2pArgs(const ncclComm* comm, const P2pLaunch& l, hipStream_t 
   a.elementwise = comm->tune.forceElementwise;
   for (size_t i = 0; i < l.streams.size(); i++) a.st[i] = l.streams[i];
   for (size_t i = 0; i < l.msgs.size(); i++) a.msg[i] = l.msgs[i];
-  NCCL_AMD_LAUNCH((p2pKernel<S, M>), dim3(l.grid), dim3(kThreads), 0, stream, a);
+  if (ll) NCCL_AMD_LAUNCH((p2pLLKernel<S, M>), dim3(l.grid), dim3(kThreads), 0, stream, a);
+  else NCCL_AMD_LAUNCH((p2pKernel<S, M>), dim3(l.grid), dim3(kThreads), 0, stream, a);
 }
 template <int SMALL = 2>
 inline ncclResult_t launchP2pT(const ncclComm* comm, const P2pLaunch& l, hipStream_t stream) {
   if (l.streams.size() > (size_t)kP2pMaxStreams || l.msgs.size() > (size_t)kP2pMaxMsgs || l.grid < 1) return ncclInternalError;
-  if (l.streams.size() <= (size_t)SMALL && l.msgs.size() <= (size_t)SMALL) launchP2pArgs<SMALL, SMALL>(comm, l, stream);
-  else launchP2pArgs<kP2pMaxStreams, kP2pMaxMsgs>(comm, l, stream);
+  bool ll = false;
+  for (const P2pMsg& m : l.msgs) ll = ll || m.ll != 0;
+  if (ll && comm->p2pLLChannels < 1) return ncclInternalError;
+  if (l.streams.size() <= (size_t)SMALL && l.msgs.size() <= (size_t)SMALL) launchP2pArgs<SMALL, SMALL>(comm, l, stream, ll);
+  else launchP2pArgs<kP2pMaxStreams, kP2pMaxMsgs>(comm, l, stream, ll);
   HIPCHECK(hipGetLastError());
   return ncclSuccess;
 }

@@ -14,6 +14,11 @@
 // never apart. The unfinished stream of the smallest round anywhere then has every earlier launch of both its ranks
 // complete, so both its workgroups are resident: no deadlock, however each rank packs its rounds.
 //
+// A message of at most NCCL_AMD_P2P_LL_BYTES whose LL cut (device_abi.h p2pLLCut) fits the communicator's p2p LL
+// channels is tagged LL (P2pMsg::ll) and carries that cut instead: a function of the byte count and rank-0 constants
+// too, so both ends tag it alike. A launch that holds an LL message runs p2pLLKernel, any other p2pKernel as before;
+// LL and staged messages of a pair keep separate sequences, each matching in issue order within its kind.
+//
 // ncclAlltoAll / ncclGather whose sendbuff lies in a symmetric window do not expand: they are planned and launched as
 // one collective on the zero-copy kernel (symA2ASubmit below, enqueue.cc planSymA2A).
 #include <string.h>
@@ -35,6 +40,13 @@ P2pCut p2pCutFor(const ncclComm* comm, size_t bytes) {
   return p2pCut(bytes, (uint64_t)comm->tune.p2pChunkBytes, std::min(comm->tune.p2pMinCh, mx), mx);
 }
 
+// The LL cut of a message, nch == 0 when it is staged: LL is off (no line area), the message exceeds the threshold, or
+// it needs more channels than the area has.
+static P2pCut p2pLLCutFor(const ncclComm* comm, size_t bytes) {
+  if (comm->p2pLLChannels < 1 || bytes > (size_t)comm->tune.p2pLLBytes) return {0, 0};
+  return p2pLLCut(bytes, (uint64_t)comm->p2pLLLineBytes, comm->p2pLLChannels);
+}
+
 ncclResult_t p2pPlan(ncclComm* comm, const std::vector<P2pOp>& ops, P2pPlan* plan) {
   const int n = comm->nRanks, me = comm->rank;
   plan->self.clear();
@@ -45,8 +57,10 @@ ncclResult_t p2pPlan(ncclComm* comm, const std::vector<P2pOp>& ops, P2pPlan* pla
   for (const P2pOp& op : ops) {
     if (op.peer < 0 || op.peer >= n) return ncclInternalError;  // (checked at the entry point)
     if (op.bytes == 0) continue;  // both sides know: counts match. No handshake, no place in the order
-    const P2pCut cut = p2pCutFor(comm, op.bytes);
-    (op.recv ? recvFrom : sendTo)[op.peer].push_back({(uint64_t)(uintptr_t)op.buff, (uint64_t)op.bytes, cut.part, (uint32_t)cut.nch, 0});
+    P2pCut cut = p2pLLCutFor(comm, op.bytes);
+    const uint32_t ll = cut.nch > 0;
+    if (!ll) cut = p2pCutFor(comm, op.bytes);
+    (op.recv ? recvFrom : sendTo)[op.peer].push_back({(uint64_t)(uintptr_t)op.buff, (uint64_t)op.bytes, cut.part, (uint32_t)cut.nch, ll});
     remote = remote || op.peer != me;
   }
   // round 0: self sends and recvs pair up in issue order (reference enqueue.cc:1158-1166)
@@ -122,9 +136,10 @@ ncclResult_t p2pPlan(ncclComm* comm, const std::vector<P2pOp>& ops, P2pPlan* pla
   return ncclSuccess;
 }
 
-// Host-side guard before a p2pKernel launches (enqueue.cc checkGrid's rule): the grid within the co-resident cap,
-// every channel index within the channels the staging slab, flag block and counters were allocated for, the
-// workgroup ranges and message ranges of the streams exactly the launch's.
+// Host-side guard before a p2pKernel / p2pLLKernel launches (enqueue.cc checkGrid's rule): the grid within the
+// co-resident cap, every channel index within the channels the staging slab, flag block and counters were allocated
+// for — an LL message's within the p2p LL line area's, its part within a slot's lines —, the workgroup ranges and
+// message ranges of the streams exactly the launch's.
 static ncclResult_t p2pCheckGrid(const ncclComm* comm, const P2pLaunch& l) {
   bool good = l.grid >= 1 && l.grid <= comm->chanCap && !l.streams.empty() && l.streams.size() <= (size_t)kP2pMaxStreams &&
               l.msgs.size() <= (size_t)kP2pMaxMsgs;
@@ -134,7 +149,11 @@ static ncclResult_t p2pCheckGrid(const ncclComm* comm, const P2pLaunch& l) {
     const P2pStream& s = l.streams[i];
     good = s.wgOff == off && s.nch >= 1 && s.nch <= comm->maxChannels && s.msgOff == moff && s.peer < comm->nRanks &&
            s.peer != comm->rank;
-    for (size_t k = 0; good && k < s.nMsgs; k++) good = moff + k < l.msgs.size() && l.msgs[moff + k].nch <= s.nch;
+    for (size_t k = 0; good && k < s.nMsgs; k++) {
+      good = moff + k < l.msgs.size() && l.msgs[moff + k].nch <= s.nch;
+      if (good && l.msgs[moff + k].ll)
+        good = (int)l.msgs[moff + k].nch <= comm->p2pLLChannels && l.msgs[moff + k].part * 16 <= comm->p2pLLLineBytes;
+    }
     off += s.nch;
     moff += s.nMsgs;
   }
@@ -151,6 +170,8 @@ ncclResult_t p2pLaunchPlan(ncclComm* comm, const P2pPlan& plan, hipStream_t stre
   for (const P2pLaunch& l : plan.launches) {
     TRACE("p2p launch: rank %d rounds %d..%d, %zu streams, %zu messages, %d workgroups", comm->rank, l.firstRound,
           l.lastRound, l.streams.size(), l.msgs.size(), l.grid);
+    const size_t nLL = std::count_if(l.msgs.begin(), l.msgs.end(), [](const P2pMsg& m) { return m.ll != 0; });
+    if (nLL) TRACE("p2p launch: rank %d rounds %d..%d, ll messages %zu", comm->rank, l.firstRound, l.lastRound, nLL);
     NCCLCHECK(launchP2pKernel(comm, l, stream));
   }
   if (comm->fdServer && !plan.launches.empty()) {  // (enqueue.cc noteLaunch)

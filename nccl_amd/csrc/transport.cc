@@ -14,6 +14,8 @@
 #include <string.h>
 #include <unistd.h>
 
+#include <algorithm>
+
 #include "core.h"
 
 namespace ncclamd {
@@ -27,10 +29,15 @@ static size_t flagWordBytes(const ncclComm* c) {
 static size_t llOffset(const ncclComm* c) { return (flagWordBytes(c) + 4095) / 4096 * 4096; }
 // LL area, then the LL64 area of the same geometry (device_abi.h)
 static size_t ll64Offset(const ncclComm* c) { return llOffset(c) + (size_t)c->llChannels * 2 * c->nRanks * c->llBytes; }
-// then the mapping-check area (mapcheck.cc): 2 rows x NCCL_AMD_MAX_RANKS x 16 bytes, used once at init
-static size_t probeOffset(const ncclComm* c) {
+// then the p2p LL area (device_abi.h; empty unless NCCL_AMD_P2P_LL_BYTES is set: the layout is then the one without it)
+static size_t p2pLLOffset(const ncclComm* c) {
   return (ll64Offset(c) + (size_t)c->llChannels * 2 * c->nRanks * c->llBytes + 255) / 256 * 256;
 }
+static size_t p2pLLBytes(const ncclComm* c) {
+  return (size_t)c->p2pLLChannels * kP2pLLDepth * c->nRanks * c->p2pLLLineBytes;
+}
+// then the mapping-check area (mapcheck.cc): 2 rows x NCCL_AMD_MAX_RANKS x 16 bytes, used once at init
+static size_t probeOffset(const ncclComm* c) { return (p2pLLOffset(c) + p2pLLBytes(c) + 255) / 256 * 256; }
 static size_t flagsBytes(const ncclComm* c) { return probeOffset(c) + kMapProbeBytes; }
 
 // Device memory this communicator holds on its GPU (ncclCommMemStats): staging slab, flag/LL lines,
@@ -63,6 +70,12 @@ ncclResult_t transportSetup(ncclComm* comm) {
     comm->peerFlags[0] = comm->flags;
     return ncclSuccess;
   }
+  // the LL line area of ncclSend / ncclRecv, only when the knob is set (rank 0's, agreed before this call); sized for
+  // the knob's channels, lowered to the co-resident cap once that is known (commAllocDevState)
+  if (comm->tune.p2pLLBytes > 0) {
+    comm->p2pLLChannels = std::min(comm->tune.p2pLLNch, comm->maxChannels);
+    comm->p2pLLLineBytes = (size_t)comm->tune.p2pLLLineBytes;
+  }
   size_t sb = stagingBytes(comm), fb = flagsBytes(comm);
   {
     // only the allocations themselves are serialized with imports / releases (gMapMu): the fd server thread
@@ -82,6 +95,9 @@ ncclResult_t transportSetup(ncclComm* comm) {
   HIPCHECK(hipDeviceSynchronize());
   INFO("rank %d dev %d: staging %zu MiB (%d ch x %d slots x %zu KiB), flags %zu KiB", comm->rank, comm->device,
        sb >> 20, comm->maxChannels, comm->nSlots, comm->slotBytes >> 10, fb >> 10);
+  if (comm->p2pLLChannels > 0)
+    INFO("rank %d dev %d: p2p LL lines %zu KiB (%d ch x %d slots x %d ranks x %zu B)", comm->rank, comm->device,
+         p2pLLBytes(comm) >> 10, comm->p2pLLChannels, kP2pLLDepth, comm->nRanks, comm->p2pLLLineBytes);
   return ncclSuccess;
 }
 
@@ -183,7 +199,8 @@ ncclResult_t transportDrainCredits(ncclComm* comm) {
         if (p == comm->rank) continue;
         done = flg[flagIndex(c, FLG_RS_ACK, p)] >= ctr[ctrIndex(c, CTR_SEND_RS, p)] &&
                flg[flagIndex(c, FLG_AG_ACK, p)] >= ctr[ctrIndex(c, CTR_SEND_AG, p)] &&
-               flg[flagIndex(c, FLG_PULL_ACK, p)] >= ctr[ctrIndex(c, CTR_PULL_PUB, 0)];
+               flg[flagIndex(c, FLG_PULL_ACK, p)] >= ctr[ctrIndex(c, CTR_PULL_PUB, 0)] &&
+               flg[flagIndex(c, FLG_P2PLL_ACK, p)] >= ctr[ctrIndex(c, CTR_P2PLL_SEND, p)];
       }
     if (done) return ncclSuccess;
     if (waited >= limitMs) {
@@ -253,9 +270,15 @@ ncclResult_t commAllocDevState(ncclComm* comm) {
   // area was sized for the full count; host planning and the kernel's batch modulus use this value)
   d.llOffset = llOffset(comm);
   d.ll64Offset = ll64Offset(comm);  // both before the cap below: the areas were sized for the full count
+  d.p2pLLOffset = p2pLLOffset(comm);  // (and this one: it follows them)
   if (comm->llChannels > comm->chanCap && comm->chanCap > 0) comm->llChannels = comm->chanCap;
   d.llBytes = comm->llBytes;
   d.llChannels = comm->llChannels;
+  // the p2p LL area likewise: laid out for the channels allocated, used on at most half the co-resident cap (a
+  // round's send and recv streams share a launch, p2p.cc p2pMaxChannels)
+  if (comm->p2pLLChannels > comm->chanCap / 2) comm->p2pLLChannels = comm->chanCap / 2;
+  d.p2pLLLineBytes = comm->p2pLLLineBytes;
+  d.p2pLLChannels = comm->p2pLLChannels;
   void* dAbort = nullptr;
   void* dErr = nullptr;
   HIPCHECK(hipHostGetDevicePointer(&dAbort, comm->hostAbort, 0));
