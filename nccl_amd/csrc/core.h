@@ -289,6 +289,7 @@ struct CommTuning {
   int symA2A;               // NCCL_AMD_SYM_A2A: AlltoAll / Gather with the sendbuff in a symmetric window run zero-copy
   int symOneShot;           // NCCL_AMD_SYM_ONESHOT: caller promises out-of-place window AllReduces
   int symWtPublish;         // NCCL_AMD_SYM_WT: symmetric kernels publish with write-through stores, no L2 write-back
+  int symWideAcc;           // NCCL_AMD_SYM_WIDE_ACC: zero-copy fp16 / bf16 / fp8 Sum and Avg accumulate in f32, one rounding
   int localRegister;        // NCCL_LOCAL_REGISTER: ncclCommRegister maps buffers into peers (zero-copy collectives)
   int graphRegister;        // NCCL_GRAPH_REGISTER: buffers of captured collectives are registered automatically
   int noAggregation;        // NCCL_AMD_NO_AGGREGATION

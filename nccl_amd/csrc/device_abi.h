@@ -208,6 +208,8 @@ struct SymArgs {
   int wtPublish;       // bytes peers read (AR fold result, AG own block) stored write-through: no L2 write-back
   int regMode;         // buffers registered with ncclCommRegister: device-side pointer exchange (above)
   int relFence;        // publish with a system release fence even after write-through stores (across devices)
+  int wide;            // NCCL_AMD_SYM_WIDE_ACC: 1 Sum, 2 Avg of a 16- / 8-bit float folds in f32 (kernels.h foldRangeWide)
+  float wideScale;     // ... Avg: 1.0f / nRanks, computed here on the host; the sum is multiplied by it once
 };
 
 // Mapping check at communicator init (mapcheck.cc, kernels.hip mapCheckKernel): the words this rank stores into

@@ -233,6 +233,10 @@ void loadTuning(CommTuning* t) {
   // write-through publish in the symmetric kernels: n = 2 one-GPU rehearsal 0.291-0.295 -> 0.234-0.241 ms at
   // 256 MiB fp32 (no per-channel L2 write-back; profiles/r02_sym_wt_ab_onegpu.txt)
   t->symWtPublish = (int)paramInt("NCCL_AMD_SYM_WT", 1);
+  // f32 accumulators and one rounding for fp16 / bf16 / fp8 Sum and Avg on the zero-copy kernels, as the reference's
+  // symmetric kernels (kernels.h foldRangeWide). 0 (default): the per-hop fold, bit-equal to the ring
+  // order of every other path (§6)
+  t->symWideAcc = (int)paramInt("NCCL_AMD_SYM_WIDE_ACC", 0) != 0;
   // reference register.cc:16 / enqueue.cc:283 (both default on): ncclCommRegister'd buffers and, under stream
   // capture, the captured collectives' buffers run the zero-copy kernel (register.cc)
   t->localRegister = (int)paramInt("NCCL_LOCAL_REGISTER", 1);
@@ -1060,6 +1064,21 @@ ncclResult_t planColl(const CollInfo& info, LaunchPlan& p, SymPlan& sp, int* kin
       sp.args.part = part;
       sp.nChannels = nch;
       sp.stream = info.stream;
+      // NCCL_AMD_SYM_WIDE_ACC: the built-in Sum and Avg of a 16- / 8-bit float fold in f32 with one rounding. From the
+      // agreed knob, the datatype and the op alone, so every rank runs the same kernel. Ops whose argument depends on
+      // the datatype (MinMax, user PreMulSum), Prod and every other type keep the per-hop fold, as in the reference
+      // (src/device/symmetric/primitives.cuh:239-241)
+      const bool smallFloat = info.datatype == ncclFloat16 || info.datatype == ncclBfloat16 ||
+                              info.datatype == ncclFloat8e4m3 || info.datatype == ncclFloat8e5m2;
+      if (comm->tune.symWideAcc && smallFloat && sp.coll != 3 /*SYM_AG*/ && (info.op == ncclSum || info.op == ncclAvg)) {
+        sp.args.wide = info.op == ncclAvg ? 2 : 1;
+        sp.args.wideScale = 1.0f / (float)n;
+      }
+      if (sp.args.wide) {
+        TRACE("%s: %s coll %d nch %d part %lu aligned %d wide 1", info.opName,
+              regMode ? "registered zero-copy" : "symmetric", sp.coll, nch, (unsigned long)part, sp.args.aligned);
+        return ncclSuccess;
+      }
       TRACE("%s: %s coll %d nch %d part %lu aligned %d", info.opName, regMode ? "registered zero-copy" : "symmetric",
             sp.coll, nch, (unsigned long)part, sp.args.aligned);
       return ncclSuccess;

@@ -10,6 +10,6 @@ hipError_t warmKernBF16() {
   return hipFuncGetAttributes(&attr, (const void*)&collKernel<bf16_t, 0, COLL_AR>);
 }
 ncclResult_t launchSymKernBF16(const SymPlan& p) {
-  return launchSymOp<bf16_t>(p);
+  return launchSymSmallFloat<bf16_t>(p);
 }
 }  // namespace ncclamd

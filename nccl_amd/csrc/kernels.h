@@ -653,6 +653,146 @@ __device__ __forceinline__ void foldRange(const Red<T, OP>& fn, int n, const cha
   }
 }
 
+// ------------------------------------------------------------------------------------ wide-accumulator fold
+//
+// The zero-copy kernels' opt-in fold of fp16 / bf16 / fp8 Sum and Avg (NCCL_AMD_SYM_WIDE_ACC; the
+// reference's symmetric kernels, src/device/symmetric/primitives.cuh:234-277): every element is decoded to f32
+// (exact), the n sources are added in f32 in foldRange's order (acc = src[0]; acc = src[k] + acc), Avg multiplies
+// the sum once by the host's 1.0f / n, and ONE conversion rounds to T. No Red<T, OP>: those round on every hop.
+//
+// Registers decide the shape. An accumulator pack is 8 (2-byte types) or 16 (fp8) VGPRs where foldRange holds 4,
+// and the loads in flight (the current and the next source's packs) cost 8 per pack as there. The kernels must
+// stay within 128 VGPRs without scratch (kCoResident), so a thread owns kWideUnroll2B / kWideUnroll1B packs per
+// batch; the register figures of both choices are in DESIGN.md §2.8. The loop is foldRange's: the next source's
+// packs load while the current one folds, and the next batch's first source while the last one does.
+// Per element and source the fold costs a decode and an add — bf16: a shift or a mask; fp16: v_cvt_f32_f16 (or
+// folded into the add as v_fma_mix_f32); fp8: half a v_cvt_pk_f32_fp8 / _bf8 — less than the per-hop fold, which
+// also rounds and repacks on every hop. The rounding (v_cvt_pk_bf16_f32, v_cvt_f16_f32, clamp + v_cvt_pk_fp8_f32 /
+// _bf8_f32) runs once per element.
+#ifndef NCCL_AMD_WIDE_UNROLL_2B
+#define NCCL_AMD_WIDE_UNROLL_2B 4
+#endif
+#ifndef NCCL_AMD_WIDE_UNROLL_1B
+#define NCCL_AMD_WIDE_UNROLL_1B 2
+#endif
+constexpr int kWideUnroll2B = NCCL_AMD_WIDE_UNROLL_2B;
+constexpr int kWideUnroll1B = NCCL_AMD_WIDE_UNROLL_1B;
+// symKernel's OP parameter of the wide kernels (never a SymPlan::devOp: the plan says SymArgs::wide)
+constexpr int kOpWideSum = 16, kOpWideAvg = 17;
+
+// T <-> f32 of the wide fold: a 16-byte pack at a time, and per element (tails, unaligned ranges) with the same
+// instructions' results, so both paths store the same bits.
+template <typename T>
+struct Wide {
+  static constexpr int EPP = 16 / sizeof(T);
+  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+  __device__ static __forceinline__ void unpack(u32x4 v, float* f) {
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      if constexpr (IsFp8<T>::value) {
+        fp8WideDecode4<IsFp8<T>::e5m2>(v[w], f + 4 * w);
+      } else if constexpr (std::is_same<T, bf16_t>::value) {
+        f[2 * w] = u32AsF32(v[w] << 16);
+        f[2 * w + 1] = u32AsF32(v[w] & 0xffff0000u);
+      } else {
+        const uint32_t d = v[w];  // (a copy: __builtin_bit_cast of the vector element itself reads element 0)
+        const h2 h = __builtin_bit_cast(h2, d);
+        f[2 * w] = (float)h.x;
+        f[2 * w + 1] = (float)h.y;
+      }
+    }
+  }
+  __device__ static __forceinline__ u32x4 pack(const float* f) {
+    u32x4 v;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      if constexpr (IsFp8<T>::value) v[w] = fp8WideEncode4<IsFp8<T>::e5m2>(f + 4 * w);
+      else v[w] = (uint32_t)fromF(f[2 * w]).x | ((uint32_t)fromF(f[2 * w + 1]).x << 16);  // v_cvt_pk_bf16_f32 / v_cvt_f16_f32 x 2
+    }
+    return v;
+  }
+  __device__ static __forceinline__ float toF(T x) {
+    if constexpr (IsFp8<T>::value) return fp8WideDecode<IsFp8<T>::e5m2>(x.x);
+    else return Traits<T>::toF(x);
+  }
+  __device__ static __forceinline__ T fromF(float f) {
+    if constexpr (IsFp8<T>::value) return T{f32ToFp8SatHw<IsFp8<T>::e5m2>(f)};
+    else return Traits<T>::fromF(f);
+  }
+};
+
+template <typename T, bool AVG>
+__device__ __forceinline__ void foldRangeWide(float scale, int n, const char* const* src, uint64_t nelem, char* dstLocal,
+                                              char* const* dstPush, int nPush, bool aligned) {
+  constexpr int EPP = Wide<T>::EPP;
+  constexpr int U = sizeof(T) > 1 ? kWideUnroll2B : kWideUnroll1B;
+  // the sum (Avg: times 1/n, one f32 multiply) as the value the conversion rounds. fp16: kept opaque, or the
+  // backend folds the multiply into v_fma_mixlo_f16(acc, scale, +0.0), which turns a -0 sum into +0 (opaqueF)
+  auto result = [&](float acc) -> float {
+    if (AVG) acc = acc * scale;
+    return std::is_same<T, half_t>::value ? opaqueF(acc) : acc;
+  };
+  auto element = [&](uint64_t t) {
+    float acc = Wide<T>::toF(((const T*)src[0])[t]);
+    for (int k = 1; k < n; k++) acc = Wide<T>::toF(((const T*)src[k])[t]) + acc;
+    const T out = Wide<T>::fromF(result(acc));
+    if (dstLocal) ((T*)dstLocal)[t] = out;
+    for (int p = 0; p < nPush; p++) storeRemoteElt((T*)dstPush[p] + t, out);
+  };
+  if (!aligned) {
+    for (uint64_t t = threadIdx.x; t < nelem; t += kThreads) element(t);
+    return;
+  }
+  const uint64_t npk = nelem / EPP;
+  const uint64_t step = (uint64_t)U * kThreads;
+  float acc[U][EPP];
+  u32x4 cur[U], nxt[U];
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+    const uint64_t i = threadIdx.x + (uint64_t)u * kThreads;
+    if (i < npk) cur[u] = __builtin_nontemporal_load((const u32x4*)src[0] + i);
+  }
+  for (uint64_t base = threadIdx.x; base < npk; base += step) {
+    for (int k = 0; k < n; k++) {
+      const bool last = k + 1 == n;
+      if (!last || base + step < npk) {  // the next source's packs; behind the last source, the next batch's first
+        const u32x4* s = (const u32x4*)src[last ? 0 : k + 1];
+        const uint64_t b = last ? base + step : base;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          const uint64_t i = b + (uint64_t)u * kThreads;
+          if (i < npk) nxt[u] = __builtin_nontemporal_load(s + i);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        float x[EPP];
+        Wide<T>::unpack(cur[u], x);
+#pragma unroll
+        for (int e = 0; e < EPP; e++) acc[u][e] = k == 0 ? x[e] : x[e] + acc[u][e];
+        cur[u] = nxt[u];
+      }
+    }
+    LocalStore ls(dstLocal, base - threadIdx.x);
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const uint64_t i = base + (uint64_t)u * kThreads;
+      if (i >= npk) continue;
+#pragma unroll
+      for (int e = 0; e < EPP; e++) acc[u][e] = result(acc[u][e]);
+      const u32x4 out = Wide<T>::pack(acc[u]);
+      if (dstLocal) ls.put(threadIdx.x + u * kThreads, out);
+      for (int p = 0; p < nPush; p++) {  // (resource rebased on the batch's first pack, as in foldRange)
+        if (NCCL_AMD_BUFFER_STORES)
+          storeRemoteAt(remoteRsrc((u32x4*)dstPush[p] + (base - threadIdx.x)), (threadIdx.x + u * kThreads) * 16u, out);
+        else storeRemote((u32x4*)dstPush[p] + i, out);
+      }
+    }
+  }
+  const uint64_t t = npk * EPP + threadIdx.x;  // < 16-byte tail of the range
+  if (t < nelem) element(t);
+}
+
 
 // ------------------------------------------------------------------------------------ collective kernel
 
@@ -2227,7 +2367,13 @@ __global__ void __launch_bounds__(kThreads) kCoResident symKernel(SymArgs a) {
     opArg = 0;
     __builtin_memcpy(&opArg, a.redArgPtr, sizeof(T));
   }
-  const Red<T, OP> fn(opArg);
+  // the wide kernels (OP = kOpWideSum / kOpWideAvg) fold with foldRangeWide and SymArgs::wideScale, no functor
+  constexpr bool kWide = OP == kOpWideSum || OP == kOpWideAvg;
+  const Red<T, kWide ? (int)DEV_SUM : OP> fn(opArg);
+  auto fold = [&](uint64_t nelem, char* dstLocal, int nPush, bool al) {
+    if constexpr (kWide) foldRangeWide<T, OP == kOpWideAvg>(a.wideScale, n, sh.srcPtr, nelem, dstLocal, sh.pushPtr, nPush, al);
+    else foldRange<T, OP>(fn, n, sh.srcPtr, nelem, dstLocal, sh.pushPtr, nPush, al);
+  };
   // Registered mode reads peers' buffers at the pointers they hand over at ENTER. After a device error of this comm (a
   // kernel mismatch, a timeout) the ranks' epochs no longer match: an ENTER wait could pass on a peer's flag of an older
   // collective and read pointers whose mappings are gone. The error word is only written by this comm's kernels, which
@@ -2304,7 +2450,7 @@ __global__ void __launch_bounds__(kThreads) kCoResident symKernel(SymArgs a) {
       if (tid == 0)
         for (int k = 0; k < n; k++) sh.srcPtr[k] = sh.send[(owner + 1 + k) % n] + x * ts;
       __syncthreads();
-      foldRange<T, OP>(fn, n, sh.srcPtr, end - x, sh.recv[me] + x * ts, nullptr, 0, aligned);
+      fold(end - x, sh.recv[me] + x * ts, 0, aligned);
       __syncthreads();
       x = end;
     }
@@ -2319,7 +2465,7 @@ __global__ void __launch_bounds__(kThreads) kCoResident symKernel(SymArgs a) {
     const bool push = COLL == SYM_AR && wt;  // peers read it in the pull phase
     if (tid == 0) sh.pushPtr[0] = dst;
     __syncthreads();
-    foldRange<T, OP>(fn, n, sh.srcPtr, hi - lo, push ? nullptr : dst, sh.pushPtr, push ? 1 : 0, aligned);
+    fold(hi - lo, push ? nullptr : dst, push ? 1 : 0, aligned);
     __syncthreads();
   }
   if (ok && COLL == SYM_AR) {
@@ -2368,6 +2514,24 @@ inline ncclResult_t launchSymOp(const SymPlan& p) {
   }
   WARN("internal: op %d unsupported for this type", p.devOp);
   return ncclInternalError;
+}
+// fp16 / bf16 / fp8 (their units alone instantiate the wide kernels): a plan marked wide runs them
+template <typename T, int OP>
+inline ncclResult_t launchSymWideTyped(const SymPlan& p) {
+  switch (p.coll) {
+    case SYM_AR: NCCL_AMD_LAUNCH((symKernel<T, OP, SYM_AR>), dim3(p.nChannels), dim3(kThreads), 0, p.stream, p.args); break;
+    case SYM_AR1: NCCL_AMD_LAUNCH((symKernel<T, OP, SYM_AR1>), dim3(p.nChannels), dim3(kThreads), 0, p.stream, p.args); break;
+    case SYM_RS: NCCL_AMD_LAUNCH((symKernel<T, OP, SYM_RS>), dim3(p.nChannels), dim3(kThreads), 0, p.stream, p.args); break;
+    default: WARN("internal: no wide kernel for the symmetric collective %d", p.coll); return ncclInternalError;
+  }
+  HIPCHECK(hipGetLastError());
+  return ncclSuccess;
+}
+template <typename T>
+inline ncclResult_t launchSymSmallFloat(const SymPlan& p) {
+  if (p.args.wide == 1) return launchSymWideTyped<T, kOpWideSum>(p);
+  if (p.args.wide == 2) return launchSymWideTyped<T, kOpWideAvg>(p);
+  return launchSymOp<T>(p);
 }
 template <typename T>
 inline ncclResult_t launchSymIntOp(const SymPlan& p) {

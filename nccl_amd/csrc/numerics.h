@@ -424,6 +424,35 @@ __device__ inline uint32_t fp8Encode4(const float* f) {
   }
   return ((uint32_t)w | set) & ~clr;
 }
+
+// ---- the wide fold's conversions (kernels.h foldRangeWide): f32 accumulators, one rounding ----
+// Decode: the paired instructions alone. They decode every NaN code as a negative NaN (fp8Decode4 restores the
+// sign with a shift and a v_bfi per element and source); a NaN's sign is no part of the wide contract, and the
+// element-wise decode below is the same instruction, so the pack path and the element path agree on every code.
+template <bool E5M2>
+__device__ inline void fp8WideDecode4(uint32_t w, float* f) {
+  const fp8v2f lo = E5M2 ? __builtin_amdgcn_cvt_pk_f32_bf8((int)w, false) : __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+  const fp8v2f hi = E5M2 ? __builtin_amdgcn_cvt_pk_f32_bf8((int)w, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+  f[0] = lo.x, f[1] = lo.y, f[2] = hi.x, f[3] = hi.y;
+}
+template <bool E5M2>
+__device__ inline float fp8WideDecode(uint8_t v) {
+  return E5M2 ? __builtin_amdgcn_cvt_f32_bf8((int)v, 0) : __builtin_amdgcn_cvt_f32_fp8((int)v, 0);
+}
+// Encode: clamp to +-max finite (Inf saturates) with compare-and-select, which keeps a NaN where v_max_f32 /
+// v_min_f32 would return the bound, then round to nearest even straight from f32; fp8Encode4 turns the
+// instruction's NaN code into sign | 0x7f. f32ToFp8SatHw does the same per element.
+template <bool E5M2>
+__device__ inline uint32_t fp8WideEncode4(const float* acc) {
+  const float mx = E5M2 ? 57344.0f : 448.0f;
+  float c[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    c[i] = acc[i] > mx ? mx : acc[i];
+    c[i] = c[i] < -mx ? -mx : c[i];
+  }
+  return fp8Encode4<E5M2>(c);
+}
 #endif
 
 // ---- 1-byte integer Sum / MinMax on four bytes per dword (SWAR) ----
