@@ -26,7 +26,7 @@ HDRS     := $(wildcard $(SRCDIR)/*.h) include/nccl.h include/nccl_device.h inclu
 
 all: lib oracle numerics-host bootstrap-test tuner-test nccl-perf comm-examples plan-test mapcheck-test xgmi-probe atomicity-probe \
      fp8-probe release-probe reuse-probe export-check-test barrier-probe bcast-plan-test bcast-example p2p-plan-test sendrecv-example \
-     rma-plan-test sym-a2a-plan-test comm-split-test devapi-kernels devapi-layout-test devapi-example \
+     rma-plan-test sym-a2a-plan-test sym-bcast-plan-test comm-split-test devapi-kernels devapi-layout-test devapi-example \
      devapi-rc-kernels devapi-rc-host-test devapi-rc-example devapi-lla2a-kernels devapi-lla2a-host-test \
      devapi-lla2a-example
 
@@ -173,6 +173,16 @@ tests/native/sym_a2a_plan_test: tests/native/sym_a2a_plan_test.cc $(SRCDIR)/devi
 	  -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
 
 .PHONY: sym-a2a-plan-test
+
+# CPU sweep of the cut the zero-copy Broadcast kernel walks (device_abi.h symBcastOwner / symBcastDirect / symBcastCut):
+# a stand-alone host program, built under ASan+UBSan (host code only)
+sym-bcast-plan-test: tests/native/sym_bcast_plan_test
+
+tests/native/sym_bcast_plan_test: tests/native/sym_bcast_plan_test.cc $(SRCDIR)/device_abi.h
+	$(CXX) -g -O1 -fno-omit-frame-pointer -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude \
+	  -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
+
+.PHONY: sym-bcast-plan-test
 
 # a C-ABI caller of ncclSend / ncclRecv / ncclAlltoAll written against include/nccl.h only (links with -lnccl alone)
 sendrecv-example: tests/native/sendrecv_example

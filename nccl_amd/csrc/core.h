@@ -287,6 +287,7 @@ struct CommTuning {
   int parseError;           // nonzero: NCCL_ALGO / NCCL_PROTO did not parse; every rank's init fails (ncclInvalidUsage)
   int symDisable;          // NCCL_AMD_SYM_DISABLE
   int symA2A;               // NCCL_AMD_SYM_A2A: AlltoAll / Gather with the sendbuff in a symmetric window run zero-copy
+  int symBcast;             // NCCL_AMD_SYM_BCAST: Broadcast with the recvbuff in a symmetric window runs zero-copy (default 0)
   int symOneShot;           // NCCL_AMD_SYM_ONESHOT: caller promises out-of-place window AllReduces
   int symWtPublish;         // NCCL_AMD_SYM_WT: symmetric kernels publish with write-through stores, no L2 write-back
   int symWideAcc;           // NCCL_AMD_SYM_WIDE_ACC: zero-copy fp16 / bf16 / fp8 Sum and Avg accumulate in f32, one rounding
@@ -540,6 +541,7 @@ struct SymPlan {  // one symmetric (window) kernel launch
   hipStream_t stream;
   SymArgs args;
   SymA2AArgs a2a;       // coll SYM_A2A / SYM_GATHER: symA2AKernel's arguments (args unused)
+  SymBcastArgs bcast;   // coll SYM_BCAST: symBcastKernel's arguments (args unused)
   RegAlloc* regUse[2];  // registered mode: the send / recv registrations it runs on (their lastEv, register.cc)
   bool bounced;         // runs on the bounce allocation: `bounce` copies around the launch (bounceLaunch)
   BounceCopy bounce;

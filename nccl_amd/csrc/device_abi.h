@@ -343,6 +343,52 @@ struct SymA2AArgs {
   int pad;
 };
 
+// ---- zero-copy Broadcast on symmetric windows (kernels.h symBcastKernel, enqueue.cc planSymBcast) ----
+// The payload of `bytes` is cut into n - 1 owner blocks of alignUp(ceil(bytes / (n - 1)), 16) bytes, one per non-root
+// (trailing blocks short or empty); non-root r owns block symBcastOwner(r): it pulls that block from the root and
+// every peer pulls it from r. The root owns none. The direct variant (n == 2, or a block below one channel's minimum)
+// has ONE block, the whole payload, which every non-root pulls from the root. Every block is cut into channel parts
+// like an AlltoAll block (symA2ACut / symA2APart over the block size), so channel c moves part c of every block.
+// From bytes, n and rank-uniform constants alone: every rank launches the same grid and runs the same handshakes.
+// Host-callable so that tests/native/sym_bcast_plan_test walks exactly what the kernel walks.
+__host__ __device__ inline int symBcastOwner(int r, int root, int n) { return (r - root - 1 + n) % n; }  // root: n - 1
+__host__ __device__ inline bool symBcastDirect(uint64_t bytes, int n, uint64_t minChannelBytes) {
+  return n == 2 || bytes < (uint64_t)(n - 1) * minChannelBytes;
+}
+struct SymBcastCut {
+  int nch;         // channels of the launch
+  int blocks;      // 1 (direct) or n - 1
+  uint64_t block;  // bytes per block (the last ones shorter: blockLenOf(bytes, block, q))
+  uint64_t part;   // bytes per channel within a block
+};
+// chanBytes: the bytes one channel should at least move (minChannelBytes, or a tuner's channel count restated)
+__host__ __device__ inline SymBcastCut symBcastCut(uint64_t bytes, int n, bool direct, uint64_t chanBytes, int minCTAs,
+                                                   int cap) {
+  SymBcastCut c;
+  c.blocks = direct ? 1 : n - 1;
+  c.block = direct ? bytes : ((bytes + (uint64_t)(n - 1) - 1) / (uint64_t)(n - 1) + 15) / 16 * 16;
+  const SymA2ACut ch = symA2ACut(c.block, chanBytes, minCTAs, cap);
+  c.nch = ch.nch;
+  c.part = ch.part;
+  return c;
+}
+// Kernel arguments: every rank's recvbuff as mapped in this process (the same offset in every rank's window) and, on
+// the root, its sendbuff, which needs no window (no peer reads it; elsewhere the field is never read).
+struct SymBcastArgs {
+  const DevComm* comm;
+  char* recv[NCCL_AMD_MAX_RANKS];
+  const char* send;
+  uint64_t bytes;
+  uint64_t block;   // SymBcastCut
+  uint64_t part;
+  int root;
+  int direct;       // no MID round: every non-root pulls the whole payload from the root
+  int elementwise;  // NCCL_AMD_FORCE_ELEMENTWISE
+  int wtPublish;    // bytes peers read (the root's copy, an owner's block) stored write-through (SymArgs::wtPublish)
+  int relFence;     // publish with a system release fence even after write-through stores (SymArgs::relFence)
+  int pad;
+};
+
 // One message of a stream, and one stream = the in-order messages of one group to (recv == 0) or from one peer.
 // Stream i runs on workgroups wgOff .. wgOff + nch - 1 of its launch, workgroup wgOff + j on physical channel j, which
 // walks the stream's messages in order and skips those cut into j or fewer parts. An LL message (ll != 0) carries the

@@ -229,6 +229,10 @@ void loadTuning(CommTuning* t) {
   // ncclAlltoAll / ncclGather whose sendbuff lies in a symmetric window pull straight from the peers' windows
   // (symA2AKernel); 0: the staged send / recv expansion whatever the buffers are
   t->symA2A = (int)paramInt("NCCL_AMD_SYM_A2A", 1);
+  // ncclBroadcast / ncclBcast whose recvbuff lies in a symmetric window pull the payload out of the peers' windows
+  // (symBcastKernel). 0 (default): the staged plan whatever the buffers are — no xGMI link has
+  // measured the zero-copy one
+  t->symBcast = (int)paramInt("NCCL_AMD_SYM_BCAST", 0);
   t->symOneShot = (int)paramInt("NCCL_AMD_SYM_ONESHOT", 0);
   // write-through publish in the symmetric kernels: n = 2 one-GPU rehearsal 0.291-0.295 -> 0.234-0.241 ms at
   // 256 MiB fp32 (no per-channel L2 write-back; profiles/r02_sym_wt_ab_onegpu.txt)
@@ -766,6 +770,50 @@ static ncclResult_t planSymA2A(const CollInfo& info, SymPlan& sp, int* kind) {
   return ncclSuccess;
 }
 
+// Zero-copy Broadcast (kernels.h symBcastKernel), asked by planColl where the staged direct plan would
+// be built: NCCL_AMD_SYM_BCAST is on and [recvbuff, recvbuff + bytes) lies in the symmetric window `wr`. Every rank
+// makes the same call, so every rank decides alike from what all ranks share (n, bytes, the agreed knobs) and from its
+// own recvbuff, which lies in a symmetric window at the same offset on every rank or on none. Never from sendbuff
+// (significant on the root only, and no peer reads it), the rank or the root: that would split the kernel kinds.
+// tunedNch: a tuner plugin's channel count, applied as the symmetric AllGather plan applies it.
+static ncclResult_t planSymBcast(const CollInfo& info, ncclWindow_vidmem* wr, int tunedNch, SymPlan& sp, int* kind) {
+  ncclComm* comm = info.comm;
+  const int n = comm->nRanks;
+  const uint64_t bytes = info.count * (uint64_t)typeSize(info.datatype);  // (the entry point normalised it to bytes)
+  *kind = PLAN_SYM;
+  memset(&sp, 0, sizeof(sp));
+  sp.coll = 6 /*SYM_BCAST*/;
+  sp.datatype = ncclInt8;
+  sp.eltSize = 1;
+  sp.stream = info.stream;
+  SymBcastArgs& a = sp.bcast;
+  a.comm = comm->devComm;
+  for (int r = 0; r < n; r++) a.recv[r] = wr->peerPtr[r] + ((char*)info.recvbuff - (char*)wr->userPtr);
+  a.recv[comm->rank] = (char*)info.recvbuff;
+  a.send = comm->rank == info.root ? (const char*)info.sendbuff : nullptr;
+  a.bytes = bytes;
+  a.root = info.root;
+  a.elementwise = comm->tune.forceElementwise;
+  a.wtPublish = comm->tune.symWtPublish;
+  a.relFence = (comm->tune.protoFlags & 8) == 0;  // across devices: release fence kept (resolveFence)
+  const uint64_t minChan = (uint64_t)std::max<int64_t>(1, comm->tune.minChannelBytes);
+  a.direct = symBcastDirect(bytes, n, minChan) ? 1 : 0;
+  int cap = comm->chanCap;
+  if (n >= 3 && comm->tune.linkChannels > 0 && tunedNch == 0) cap = std::min(cap, comm->tune.linkChannels);  // CU budget
+  uint64_t chanBytes = minChan;
+  if (tunedNch > 0) {
+    const uint64_t span = a.direct ? bytes : (bytes + n - 2) / (uint64_t)(n - 1);
+    chanBytes = std::max<uint64_t>(1, (span + tunedNch - 1) / tunedNch);
+  }
+  const SymBcastCut cut = symBcastCut(bytes, n, a.direct != 0, chanBytes, comm->minCTAs, cap);
+  a.block = cut.block;
+  a.part = cut.part;
+  sp.nChannels = cut.nch;
+  TRACE("%s: symmetric %s nch %d block %lu part %lu bytes %lu root %d", info.opName, a.direct ? "direct" : "two-phase",
+        cut.nch, (unsigned long)cut.block, (unsigned long)cut.part, (unsigned long)bytes, info.root);
+  return ncclSuccess;
+}
+
 ncclResult_t planColl(const CollInfo& info, LaunchPlan& p, SymPlan& sp, int* kind) {
   ncclComm* comm = info.comm;
   const int ts = typeSize(info.datatype);
@@ -972,7 +1020,13 @@ ncclResult_t planColl(const CollInfo& info, LaunchPlan& p, SymPlan& sp, int* kin
   // Zero-copy kernels (kernels.h symKernel): buffers in NCCL_WIN_COLL_SYMMETRIC windows (reference: symmetric
   // kernels, src/enqueue.cc ncclSymkAvailable / src/device/symmetric/*), or registered with ncclCommRegister /
   // auto-registered under stream capture (reference: IPC-registered ring buffers, src/register/coll_reg.cc:
-  // 326-395). Reduce and Broadcast keep the staged path whatever their buffers are.
+  // 326-395). Reduce keeps the staged path whatever its buffers are; so does Broadcast, unless NCCL_AMD_SYM_BCAST=1
+  // and its recvbuff lies in a symmetric window (planSymBcast: windows only — registered buffers, the eager cache and
+  // graph auto-registration stay staged; an LL-sized Broadcast took its LL plan above).
+  if (info.func == FUNC_BROADCAST && comm->tune.symBcast && !comm->tune.symDisable && count > 0) {
+    ncclWindow_vidmem* wr = findSymWindow(comm, info.recvbuff, count * ts);
+    if (wr) return planSymBcast(info, wr, tunedNch, sp, kind);
+  }
   if (info.func != FUNC_REDUCE && info.func != FUNC_BROADCAST && !comm->tune.symDisable) {
     size_t sb = count * ts, rb = count * ts;
     if (info.func == FUNC_REDUCESCATTER) sb *= n;

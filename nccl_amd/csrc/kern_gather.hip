@@ -23,6 +23,8 @@ ncclResult_t launchRmaWaitKernel(const ncclComm* comm, const RmaWaitArgs& w, hip
 }
 // zero-copy ncclAlltoAll / ncclGather on symmetric windows: bytes as well (enqueue.cc planSymA2A)
 ncclResult_t launchSymA2AKernel(const SymPlan& p) { return launchSymA2AT<>(p); }
+// zero-copy ncclBroadcast / ncclBcast on symmetric windows: bytes as every Broadcast (enqueue.cc planSymBcast)
+ncclResult_t launchSymBcastKernel(const SymPlan& p) { return launchSymBcastT<>(p); }
 // Force this code object to load now (see warmKernels in kernels.hip).
 hipError_t warmKernGather() {
   hipFuncAttributes attr;

@@ -19,6 +19,7 @@
 //   llKernel   the LL protocol for small AllReduces and group batches (flag-in-data lines, no fences),
 //   symKernel  the zero-copy kernels for buffers in symmetric windows (peers' buffers pulled directly),
 //   symA2AKernel  ncclAlltoAll / ncclGather with the sendbuff in a symmetric window (one pulled copy per byte),
+//   symBcastKernel  ncclBroadcast / ncclBcast with the recvbuff in a symmetric window (NCCL_AMD_SYM_BCAST=1; pulls only),
 //   p2pKernel  ncclSend / ncclRecv: one workgroup per (direction, peer, channel) over the pair's RS slots and credits,
 //   p2pLLKernel  ... and their small messages on flag-in-data lines with a per-pair sequence and credit,
 //   rmaPutKernel / rmaWaitKernel  ncclPutSignal / ncclSignal / ncclWaitSignal: stores straight into the peer's window,
@@ -2309,8 +2310,9 @@ __global__ void __launch_bounds__(kThreads) kCoResident llKernel(LLArgs<K> a) {
 // system-scope acquire. Link bytes are those of the staged path, local HBM traffic drops from
 // 2S + 4(n-1)S/n to about 3S, and one handshake round replaces the per-slice credit protocol.
 // The epoch of each channel lives in device memory (counters[c][CTR_SYM]), so graphs replay.
-// SYM_A2A / SYM_GATHER are SymPlan::coll values only: they run symA2AKernel below, not a symKernel instantiation.
-enum SymColl { SYM_AR = 0, SYM_AR1 = 1, SYM_RS = 2, SYM_AG = 3, SYM_A2A = 4, SYM_GATHER = 5 };
+// SYM_A2A / SYM_GATHER / SYM_BCAST are SymPlan::coll values only: they run symA2AKernel / symBcastKernel below, not a
+// symKernel instantiation.
+enum SymColl { SYM_AR = 0, SYM_AR1 = 1, SYM_RS = 2, SYM_AG = 3, SYM_A2A = 4, SYM_GATHER = 5, SYM_BCAST = 6 };
 
 struct SymShared {
   ChanState st;
@@ -2592,6 +2594,93 @@ template <int UNIT = 0>
 inline ncclResult_t launchSymA2AT(const SymPlan& p) {
   if (p.nChannels < 1) return ncclInternalError;
   NCCL_AMD_LAUNCH((symA2AKernel<UNIT>), dim3(p.nChannels), dim3(kThreads), 0, p.stream, p.a2a);
+  HIPCHECK(hipGetLastError());
+  return ncclSuccess;
+}
+
+// Zero-copy Broadcast (NCCL_AMD_SYM_BCAST=1): every rank's recvbuff lies at the same offset of a
+// symmetric window, so the payload reaches every output by PULLS alone — no staging slab, no credits, and the
+// section's invariant holds: no user buffer is written remotely. The payload is cut into n - 1 owner blocks, one per
+// non-root (device_abi.h symBcastCut); per channel
+//   root   out of place, copies its parts of the whole payload from sendbuff into its own recvbuff (write-through
+//          under wtPublish, as SYM_AG's own-block copy), so peers only ever read OUTPUTS and need not know whether
+//          the root runs in place; ENTER with the release that publishes the copy; no data phase after it;
+//   ENTER  as symKernel's, with its kernel-mismatch probe;
+//   own    non-root p pulls block owner(p) from the root's recvbuff into its own, published like the root's copy:
+//          the root's links carry S / (n - 1) each, not S;
+//   MID    publish that block, wait until every owner has (the root signals at once: it owns no block);
+//   rest   pull every other owner's block from THAT owner's recvbuff, peers in the channel-rotated order;
+//   DONE   every peer has finished reading my recvbuff: the stream may overwrite it.
+// The direct variant (a.direct: n == 2 or blocks below one channel's minimum) has no MID round: every non-root pulls
+// its parts of the whole payload from the root. Every rank runs every handshake of every launched channel, empty
+// parts included, and leaves CTR_SYM and the FLG_SYM_* words at epoch e like the other symmetric kernels. The access
+// width is decided per copied part from its two addresses: 16-byte packs or bytes. Bytes, one instantiation
+// (kern_gather.hip; a template only so that that unit holds its code).
+template <bool WT>
+__device__ __forceinline__ void symBcastMove(const SymBcastArgs& a, int c, char* dstBase, const char* srcBase, int q) {
+  // channel c's part of block q, at the same payload offset on both sides
+  uint64_t lo, hi;
+  symA2APart(a.part, c, blockLenOf(a.bytes, a.block, q), lo, hi);
+  if (hi == lo) return;
+  const uint64_t off = (uint64_t)q * a.block + lo;
+  char* dst = dstBase + off;
+  const char* src = srcBase + off;
+  const bool aligned = !a.elementwise && (((uintptr_t)dst | (uintptr_t)src) & 15) == 0;
+  copyRange<uint8_t, WT>(dst, src, hi - lo, aligned);
+}
+
+template <int UNIT = 0>
+__global__ void __launch_bounds__(kThreads) kCoResident symBcastKernel(SymBcastArgs a) {
+  __shared__ SymShared sh;
+  const DevComm& dc = *a.comm;
+  const int tid = threadIdx.x, c = blockIdx.x, me = dc.rank, n = dc.nRanks, root = a.root;
+  if (c >= dc.maxChannels) return;  // (the host's grid check refuses such a launch first)
+  if (tid == 0) sh.st.abort = 0;
+  const uint64_t e = dc.counters[ctrIndex(c, CTR_SYM, 0)] + 1;
+  const bool wt = a.wtPublish != 0, twoPhase = a.direct == 0;
+  char* mine = a.recv[me];
+  bool ok;
+  if (me == root) {
+    const bool inPlace = a.send == mine;  // ncclBcast: the caller's earlier kernels wrote the payload
+    if (!inPlace) {
+      const int nb = twoPhase ? n - 1 : 1;
+      for (int q = 0; q < nb; q++) {
+        if (wt) symBcastMove<true>(a, c, mine, a.send, q);
+        else symBcastMove<false>(a, c, mine, a.send, q);
+      }
+    }
+    symSignal(dc, sh, c, FLG_SYM_ENTER, e, !wt || inPlace || a.relFence);  // publishes the payload in my output
+    ok = symWait(dc, sh, c, FLG_SYM_ENTER, e, false);
+    if (ok && twoPhase) symSignal(dc, sh, c, FLG_SYM_MID, e, false);  // I own no block: nothing to wait for
+  } else {
+    symSignal(dc, sh, c, FLG_SYM_ENTER, e, false);
+    ok = symWait(dc, sh, c, FLG_SYM_ENTER, e, true);
+    if (ok && !twoPhase) symBcastMove<false>(a, c, mine, a.recv[root], 0);
+    if (ok && twoPhase) {
+      const int q = symBcastOwner(me, root, n);
+      if (wt) symBcastMove<true>(a, c, mine, a.recv[root], q);
+      else symBcastMove<false>(a, c, mine, a.recv[root], q);
+      symSignal(dc, sh, c, FLG_SYM_MID, e, !wt || a.relFence);  // my block is in my output: publish it
+      ok = symWait(dc, sh, c, FLG_SYM_MID, e, true);
+      for (int k = 1; ok && k < n; k++) {
+        const int p = chanPeer(me, n, c, k);  // staggered by channel: all links busy
+        if (p != root) symBcastMove<false>(a, c, mine, a.recv[p], symBcastOwner(p, root, n));
+      }
+    }
+    __syncthreads();
+  }
+  if (ok) {
+    symSignal(dc, sh, c, FLG_SYM_DONE, e, false);  // drained: I no longer read any peer's recvbuff
+    ok = symWait(dc, sh, c, FLG_SYM_DONE, e, false);
+  }
+  (void)ok;  // on failure the error word is set and the epoch still advances (the comm is unusable)
+  if (tid == 0) dc.counters[ctrIndex(c, CTR_SYM, 0)] = e;
+}
+
+template <int UNIT = 0>
+inline ncclResult_t launchSymBcastT(const SymPlan& p) {
+  if (p.nChannels < 1) return ncclInternalError;
+  NCCL_AMD_LAUNCH((symBcastKernel<UNIT>), dim3(p.nChannels), dim3(kThreads), 0, p.stream, p.bcast);
   HIPCHECK(hipGetLastError());
   return ncclSuccess;
 }
