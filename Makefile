@@ -25,7 +25,8 @@ HDRS     := $(wildcard $(SRCDIR)/*.h) include/nccl.h include/nccl_device.h inclu
             include/nccl_device_ll_a2a.h
 
 all: lib oracle numerics-host bootstrap-test tuner-test nccl-perf comm-examples plan-test mapcheck-test xgmi-probe atomicity-probe \
-     fp8-probe release-probe reuse-probe export-check-test barrier-probe bcast-plan-test bcast-example p2p-plan-test sendrecv-example \
+     fp8-probe release-probe reuse-probe export-check-test barrier-probe bcast-plan-test bcast-example p2p-plan-test p2p-zc-plan-test \
+     sendrecv-example \
      rma-plan-test sym-a2a-plan-test sym-bcast-plan-test comm-split-test devapi-kernels devapi-layout-test devapi-example \
      devapi-rc-kernels devapi-rc-host-test devapi-rc-example devapi-lla2a-kernels devapi-lla2a-host-test \
      devapi-lla2a-example
@@ -154,6 +155,14 @@ tests/native/p2p_plan_test: tests/native/p2p_plan_test.cc $(SRCDIR)/p2p.cc $(PLA
 	$(PLANCXX) -o $@ tests/native/p2p_plan_test.cc $(SRCDIR)/p2p.cc $(PLANSRC) -lpthread
 
 .PHONY: p2p-plan-test
+
+# CPU test driver of the RDV (zero-copy rendezvous) planning of ncclSend / ncclRecv: kinds, descriptors, the message cap
+p2p-zc-plan-test: tests/native/p2p_zc_plan_test
+
+tests/native/p2p_zc_plan_test: tests/native/p2p_zc_plan_test.cc $(SRCDIR)/p2p.cc $(PLANDEPS)
+	$(PLANCXX) -o $@ tests/native/p2p_zc_plan_test.cc $(SRCDIR)/p2p.cc $(PLANSRC) -lpthread
+
+.PHONY: p2p-zc-plan-test
 
 # CPU test driver of the ncclPutSignal / ncclSignal / ncclWaitSignal host plan and argument checks (rma.cc, group.cc);
 # launches and the few HIP calls are stubbed

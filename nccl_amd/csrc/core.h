@@ -321,6 +321,8 @@ struct CommTuning {
   int64_t p2pLLBytes;       // NCCL_AMD_P2P_LL_BYTES: messages of up to this many bytes take LL lines (0 = off, the default)
   int64_t p2pLLLineBytes;   // NCCL_AMD_P2P_LL_LINE_BYTES: line bytes per (channel, slot, sender), a multiple of 16
   int p2pLLNch;             // NCCL_AMD_P2P_LL_NCHANNELS: channels of the line area
+  // ... and their zero-copy rendezvous protocol (device_abi.h p2pKindOf): off unless p2pZcBytes > 0
+  int64_t p2pZcBytes;       // NCCL_AMD_P2P_ZC_BYTES: messages of at least this many bytes that are not LL are RDV (0 = off)
   // size table (NCCL_AMD_SIZE_TABLE, enqueue.cc sizeTable): per rank count, the upper ends of the LL, LL128-class
   // and one-shot ranges in bytes (0 = the built-in default); loaded once at init and agreed with rank 0's
   int64_t tableLL[NCCL_AMD_MAX_RANKS + 1], tableLL128[NCCL_AMD_MAX_RANKS + 1], tableOneShot[NCCL_AMD_MAX_RANKS + 1];
@@ -383,6 +385,14 @@ struct ncclComm {
   // to chanCap / 2 after the allocation, like llChannels) and line bytes per (channel, slot, sender)
   int p2pLLChannels = 0;
   size_t p2pLLLineBytes = 0;
+  // RDV protocol of ncclSend / ncclRecv (NCCL_AMD_P2P_ZC_BYTES): channels of its area in the flag allocation (0: none
+  // allocated, no message is RDV; lowered to chanCap / 2 like p2pLLChannels), where the area lies, and the window
+  // table its senders resolve descriptors in (pinned host memory; register.cc enters and drops the windows)
+  int p2pZcChannels = 0;
+  size_t p2pZcOffset = 0;
+  ncclamd::P2pZcWinTable* p2pZcTable = nullptr;
+  const ncclamd::P2pZcWinTable* p2pZcTableDev = nullptr;  // ... as the device addresses it
+  uint32_t winSerial = 0;  // registration serial of the last window (collective, so the same on every rank)
   int chanCap = 0;  // channels per launch that stay co-resident even with several ranks per GPU
   // ranks per GPU the cap is computed from: this communicator's own table's, or, for a child of ncclCommSplit /
   // ncclCommShrink, its parent's (copied down every generation)
@@ -616,11 +626,15 @@ struct P2pOp {  // one recorded ncclSend / ncclRecv (AlltoAll / Gather / Scatter
   int peer;
   bool recv;
 };
-struct P2pLaunch {  // one p2pKernel / p2pLLKernel launch: the streams of rounds firstRound .. lastRound
+struct P2pLaunch {  // one p2pKernel / p2pLLKernel / p2pZcKernel launch: the streams of rounds firstRound .. lastRound
   int grid;
   int firstRound, lastRound;
   std::vector<P2pStream> streams;
   std::vector<P2pMsg> msgs;
+  // only in a launch that holds an RDV message (p2pZcKernel): msgs[i]'s descriptor (a received RDV message's window
+  // serial and offset, or 0: it falls back to the staged loop), and how many RDV messages it holds
+  std::vector<uint64_t> descs;
+  int nRdv = 0;
 };
 struct P2pSelfCopy {
   void* dst;

@@ -40,6 +40,16 @@
 //     reached q + 1 - kP2pLLDepth. A third area, so a stale payload of a collective can never sit where a p2p message
 //     reads a flag, and vice versa.
 //
+//   p2p RDV area (the zero-copy rendezvous protocol of ncclSend / ncclRecv, after the p2p LL area; allocated only when
+//     NCCL_AMD_P2P_ZC_BYTES > 0; kernels.h p2pZcKernel). Per channel kP2pZcChannelBytes:
+//     descriptor lines [from < NCCL_AMD_MAX_RANKS][16 bytes], one {data32, flag32, data32, flag32} line per peer, written
+//     by the RECEIVER `from` of a message into its SENDER (where the recvbuff lies: p2pZcPack), then the done row
+//     uint64 [from < NCCL_AMD_MAX_RANKS], written by the SENDER `from` into its receiver once the payload is stored.
+//     RDV message q (0-based) of an ordered pair and channel carries the line flag (uint32_t)(q + 1) (0 mapped to 1)
+//     and the done value q + 1. The two sequences (RDV messages sent to / received from a peer on a channel) are the
+//     rows P2PZC_CTR_SEND / P2PZC_CTR_RECV appended AFTER the counter block below (p2pZcCtrIndex), allocated with the
+//     area only: without the knob no byte, flag row or counter row is added.
+//
 //   counters (plain device memory, local)
 //     uint64 [channel][ctr kind < CTR_KINDS (sendRS, recvRS, sendAG, recvAG, sym, ...)][peer < NCCL_AMD_MAX_RANKS]
 //     Per-connection step counters (reference: conn->step, src/device/prims_simple.h:100-173),
@@ -49,6 +59,8 @@
 
 #define NCCL_AMD_MAX_RANKS 16
 #define NCCL_AMD_MAX_CHANNELS 256
+
+struct ncclWindow_vidmem;  // include/nccl_device.h
 
 namespace ncclamd {
 
@@ -86,7 +98,9 @@ enum DevRedOp { DEV_SUM = 0, DEV_PROD = 1, DEV_MINMAX = 2, DEV_PREMULSUM = 3, DE
 // Error codes written by a kernel into the host-visible error word.
 // DERR_MISMATCH: a peer ran another kernel kind for the same collective (registered zero-copy vs staged; the
 // wait probe in kernels.h waitAll), reported instead of waiting for the spin timeout.
-enum DevError { DERR_NONE = 0, DERR_TIMEOUT = 1, DERR_ABORT = 2, DERR_MISMATCH = 3 };
+// DERR_WINDOW: an RDV descriptor named a window this rank does not have, or a range beyond what the peer registered
+// (kernels.h p2pZcKernel): the sender stored nothing.
+enum DevError { DERR_NONE = 0, DERR_TIMEOUT = 1, DERR_ABORT = 2, DERR_MISMATCH = 3, DERR_WINDOW = 4 };
 
 struct DevComm {
   int rank;
@@ -297,6 +311,40 @@ __host__ __device__ inline P2pCut p2pLLCut(uint64_t bytes, uint64_t lineBytes, i
   c.part = (units + nch - 1) / nch;
   return c;
 }
+// The kind of a message (P2pMsg::ll), from its byte count and rank-0 constants alone, so both ends decide alike: LL when
+// its LL cut fits (llNch = p2pLLCut(..).nch > 0 and bytes <= the LL threshold: decided by the caller), else RDV when the
+// knob is set and reached, else staged. An RDV message keeps p2pCut's cut.
+enum P2pKind { P2P_STAGED = 0, P2P_LL = 1, P2P_RDV = 2 };
+__host__ __device__ inline int p2pKindOf(uint64_t bytes, bool llFits, uint64_t zcBytes) {
+  if (bytes == 0) return P2P_STAGED;
+  if (llFits) return P2P_LL;
+  return zcBytes != 0 && bytes >= zcBytes ? P2P_RDV : P2P_STAGED;
+}
+// ---- RDV: the zero-copy rendezvous protocol (kernels.h p2pZcKernel, p2p.cc, register.cc) ----
+// The 8 payload bytes of a descriptor line: the window's registration serial (24 bits; 0 = the recvbuff lies in no
+// window, both ends run the staged loop) and the recvbuff's byte offset inside that window (40 bits). Registration is
+// collective, so a serial names the same window on every rank of the communicator.
+constexpr uint32_t kP2pZcSerialMax = (1u << 24) - 1;
+constexpr uint64_t kP2pZcOffsetMax = ((uint64_t)1 << 40) - 1;
+__host__ __device__ inline uint64_t p2pZcPack(uint32_t serial, uint64_t offset) {
+  return ((uint64_t)(serial & kP2pZcSerialMax) << 40) | (offset & kP2pZcOffsetMax);
+}
+__host__ __device__ inline uint32_t p2pZcSerial(uint64_t d) { return (uint32_t)(d >> 40); }
+__host__ __device__ inline uint64_t p2pZcOffset(uint64_t d) { return d & kP2pZcOffsetMax; }
+__host__ __device__ inline uint32_t p2pZcNextSerial(uint32_t serial) { return serial >= kP2pZcSerialMax ? 1 : serial + 1; }
+// The area inside the flag allocation (byte offsets from its start `zcOffset`) and the counter rows after the counter
+// block of `maxChannels` channels.
+constexpr uint64_t kP2pZcChannelBytes = NCCL_AMD_MAX_RANKS * 16 + NCCL_AMD_MAX_RANKS * 8;
+__host__ __device__ inline uint64_t p2pZcDescOffset(uint64_t zcOffset, int c, int from) {
+  return zcOffset + (uint64_t)c * kP2pZcChannelBytes + (uint64_t)from * 16;
+}
+__host__ __device__ inline uint64_t p2pZcDoneOffset(uint64_t zcOffset, int c, int from) {
+  return zcOffset + (uint64_t)c * kP2pZcChannelBytes + NCCL_AMD_MAX_RANKS * 16 + (uint64_t)from * 8;
+}
+enum P2pZcCtr { P2PZC_CTR_SEND = 0, P2PZC_CTR_RECV = 1, P2PZC_CTR_KINDS = 2 };
+__host__ __device__ inline uint64_t p2pZcCtrIndex(int maxChannels, int c, int kind, int peer) {
+  return (uint64_t)maxChannels * CTR_KINDS * NCCL_AMD_MAX_RANKS + ((uint64_t)c * P2PZC_CTR_KINDS + kind) * NCCL_AMD_MAX_RANKS + peer;
+}
 // slices of channel part j: steps, and bytes [lo, hi) of the message at step s (sliceBounds over the whole message)
 __host__ __device__ inline int p2pSteps(uint64_t bytes, uint64_t part, uint64_t slice, int j) {
   uint64_t lo, hi;
@@ -398,7 +446,7 @@ struct P2pMsg {
   uint64_t bytes;
   uint64_t part;
   uint32_t nch;
-  uint32_t ll;  // 0 staged (p2pCut), 1 LL (p2pLLCut)
+  uint32_t ll;  // P2pKind: 0 staged (p2pCut), 1 LL (p2pLLCut), 2 RDV (p2pCut)
 };
 struct P2pStream {
   uint16_t wgOff, nch, msgOff, nMsgs;
@@ -420,6 +468,33 @@ struct P2pArgs {
   P2pMsg msg[M];
 };
 static_assert(sizeof(P2pArgs<kP2pMaxStreams, kP2pMaxMsgs>) < 4096, "kernel arguments stay under 4 KiB");
+// RDV: the window table the sender resolves a descriptor in (pinned host memory, device-readable; register.cc). Slot
+// serial % kP2pZcWindows holds the pinned ncclWindow_vidmem record of the window registered under that serial, until a
+// later registration takes the slot or the window is deregistered (serial 0: empty).
+constexpr int kP2pZcWindows = 64;
+struct P2pZcWinTable {
+  uint32_t serial[kP2pZcWindows];
+  const ::ncclWindow_vidmem* win[kP2pZcWindows];
+};
+// The argument block of p2pZcKernel, the kernel of the launches that hold an RDV message: P2pMsg cannot grow by 8 bytes
+// at 96 messages, so the descriptors ride in an array of their own that only this block has, and such a launch holds at
+// most kP2pZcMaxMsgs messages. desc[i] belongs to msg[i]: on the receiving side the planned descriptor of an RDV message
+// (baked into the arguments, so a captured graph replays it), unused otherwise.
+constexpr int kP2pZcMaxMsgs = 80;
+template <int M>
+struct P2pZcExtra {
+  const P2pZcWinTable* table;
+  uint64_t zcOffset;   // the RDV area inside every rank's flag allocation
+  int zcChannels;
+  int pad;
+  uint64_t desc[M];
+};
+template <int S, int M>
+struct P2pZcArgs {
+  P2pArgs<S, M> p;
+  P2pZcExtra<M> z;
+};
+static_assert(sizeof(P2pZcArgs<kP2pMaxStreams, kP2pZcMaxMsgs>) < 4096, "kernel arguments stay under 4 KiB");
 
 // ---- one-sided operations (kernels.h rmaPutKernel / rmaWaitKernel, rma.cc) ----
 // One put or signal (bytes == 0: a signal, no workgroup copies) and one stream = the in-order messages of one batch to

@@ -273,6 +273,9 @@ void loadTuning(CommTuning* t) {
   t->p2pLLBytes = std::max<int64_t>(0, paramInt("NCCL_AMD_P2P_LL_BYTES", 0));
   t->p2pLLLineBytes = std::max<int64_t>(16, paramInt("NCCL_AMD_P2P_LL_LINE_BYTES", 16384) / 16 * 16);
   t->p2pLLNch = (int)std::max<int64_t>(1, paramInt("NCCL_AMD_P2P_LL_NCHANNELS", 4));
+  // their zero-copy rendezvous protocol (kernels.h p2pZcKernel): messages of at least NCCL_AMD_P2P_ZC_BYTES that are not
+  // LL are stored straight into a recvbuff that lies in a registered window; 0 = off (no area, every launch as without it)
+  t->p2pZcBytes = std::max<int64_t>(0, paramInt("NCCL_AMD_P2P_ZC_BYTES", 0));
   // the size table's ranges (per rank count; NCCL_AMD_SIZE_TABLE overrides rows, the three knobs below all rows)
   (void)loadSizeTable(t, paramStr("NCCL_AMD_SIZE_TABLE"));
   t->oneShotBytes = paramInt("NCCL_AMD_ONESHOT_BYTES", 0);  // 0: size table default (2 MiB / nRanks; 2 MiB at 2 ranks)

@@ -478,10 +478,12 @@ void ncclamd::commPollAsync(ncclComm* comm) {
   if (comm->hostError && __atomic_load_n(comm->hostError, __ATOMIC_ACQUIRE) != DERR_NONE) {
     uint32_t e = __atomic_load_n(comm->hostError, __ATOMIC_ACQUIRE);
     int cur = ncclSuccess;
-    ncclResult_t r = e == DERR_ABORT ? ncclRemoteError : e == DERR_MISMATCH ? ncclInvalidUsage : ncclSystemError;
+    ncclResult_t r = e == DERR_ABORT ? ncclRemoteError : e == DERR_MISMATCH || e == DERR_WINDOW ? ncclInvalidUsage : ncclSystemError;
     if (comm->asyncResult.compare_exchange_strong(cur, r))
       WARN("rank %d: device-side %s in a collective kernel", comm->rank,
            e == DERR_TIMEOUT    ? "spin timeout (peer never arrived)"
+           : e == DERR_WINDOW   ? "window mismatch (a peer's ncclRecv named a window this rank no longer has registered, "
+                                  "or a range beyond what that peer registered; nothing was stored)"
            : e == DERR_MISMATCH ? "kernel mismatch (a peer ran the other kernel for this collective: its buffers "
                                   "are registered on some ranks only, e.g. a registration that failed on one rank)"
                                 : "abort");

@@ -22,6 +22,7 @@
 //   symBcastKernel  ncclBroadcast / ncclBcast with the recvbuff in a symmetric window (NCCL_AMD_SYM_BCAST=1; pulls only),
 //   p2pKernel  ncclSend / ncclRecv: one workgroup per (direction, peer, channel) over the pair's RS slots and credits,
 //   p2pLLKernel  ... and their small messages on flag-in-data lines with a per-pair sequence and credit,
+//   p2pZcKernel  ... and their large messages stored straight into a recvbuff that lies in a registered window,
 //   rmaPutKernel / rmaWaitKernel  ncclPutSignal / ncclSignal / ncclWaitSignal: stores straight into the peer's window,
 //              one posting wave per peer; one polling wave,
 //   oneRankKernel (PreMulSum at nRanks == 1; the nRanks == 1 copy lives in kernels.hip).
@@ -1429,6 +1430,8 @@ struct P2pShared {
   uint64_t want[NCCL_AMD_MAX_RANKS];
   uint64_t* sigPtr[1];
   uint64_t sigVal[1];
+  char* zcDst;  // RDV: the recvbuff as mapped here, and whether this message goes direct (p2pZcKernel)
+  int zcMode;
 };
 
 // Which stream of the launch this workgroup serves (streams in workgroup order)
@@ -2017,9 +2020,29 @@ __device__ __forceinline__ void llStore8(char* base, uint64_t pk, uint64_t nbyte
 // (q + 1 - kP2pLLDepth), so a stale line is never taken for a new one. The two sequences (LL messages sent to / received
 // from the peer on this channel) live in the counter rows CTR_P2PLL_SEND / CTR_P2PLL_RECV, beside the staged ones: a
 // workgroup loads and stores only its own two words.
-// The body of both kernels: LL == false is p2pKernel, the staged slice loop alone; LL == true adds the line protocol.
-template <int S, int M, bool LL>
-__device__ __forceinline__ void p2pRun(const P2pArgs<S, M>& a, P2pShared& sh) {
+// The body of the three kernels: LL == false is p2pKernel, the staged slice loop alone; LL == true adds the line
+// protocol (p2pLLKernel); ZC == true adds the rendezvous protocol as well (p2pZcKernel, below).
+//
+// RDV, the zero-copy rendezvous protocol of large messages (NCCL_AMD_P2P_ZC_BYTES; device_abi.h "p2p RDV area"): the
+// launches that hold a message tagged P2P_RDV run p2pZcKernel, whose argument block alone carries the descriptors
+// (`z`). RDV message q of the pair-channel, flag (uint32_t)(q + 1) with 0 mapped to 1:
+//   recv: lane 0 stores the planned descriptor — window serial and byte offset of the recvbuff, or serial 0 — as one
+//         flagged 16-byte line into the SENDER's descriptor line for (channel, me). It waits for nothing of this message.
+//   send: lane 0 polls that line (llPollLine), looks the serial up in this rank's window table and takes the peer's base
+//         and size from the pinned window record: the part's target is peerPtr[peer] + offset + c * part. A serial that
+//         does not resolve or a range beyond peerSize[peer] records DERR_WINDOW and nothing is stored. Then the whole
+//         workgroup copies its part from the sendbuff straight there (rmaPutKernel's copy: 16-byte write-through
+//         stores when both addresses are 16-byte aligned, which the sender alone decides, else element-wise; ragged
+//         tails), drains, releases as the put does (protoFlags 8: no fence) and stores q + 1 into the receiver's done word.
+//   recv: waits for done == q + 1, acquires. No staging slot, RS credit or RS counter moves.
+// Serial 0 (the recvbuff lies in no window): both ends run the staged slice loop below for this message — the receiver
+// knows from its own plan, the sender from the line — which moves the pair's RS sequence on both sides alike; the done
+// handshake still follows, so ONE line per (channel, peer) is enough: the receiver writes message q + 1's line only
+// after message q's done, which the sender stores after it has read message q's line. A stale line has another flag.
+// The two RDV sequences live in the rows P2PZC_CTR_SEND / P2PZC_CTR_RECV behind the counter block (device memory, so
+// graph replays advance them); a workgroup loads and stores only its own word.
+template <int S, int M, bool LL, bool ZC>
+__device__ __forceinline__ void p2pRun(const P2pArgs<S, M>& a, const P2pZcExtra<M>* z, P2pShared& sh) {
   const DevComm& dc = *a.comm;
   const int tid = threadIdx.x, me = dc.rank, nSlots = dc.nSlots;
   const P2pStream sd = a.st[p2pStreamOf(a)];
@@ -2036,8 +2059,14 @@ __device__ __forceinline__ void p2pRun(const P2pArgs<S, M>& a, P2pShared& sh) {
   const bool valid = c >= 0 && c < (int)sd.nch && c < dc.maxChannels && peer < dc.nRanks && peer != me;
   uint64_t* const ctrWord = dc.counters + ctrIndex(valid ? c : 0, recv ? CTR_RECV_RS : CTR_SEND_RS, valid ? peer : 0);
   uint64_t* const llCtrWord = dc.counters + ctrIndex(valid ? c : 0, recv ? CTR_P2PLL_RECV : CTR_P2PLL_SEND, valid ? peer : 0);
+  // (the RDV rows exist only where the area does: a channel beyond it runs no RDV message, p2p.cc p2pCheckGrid)
+  bool zcRows = false;
+  if constexpr (ZC) zcRows = valid && c < z->zcChannels;
+  uint64_t* const zcCtrWord =
+      dc.counters + p2pZcCtrIndex(dc.maxChannels, zcRows ? c : 0, recv ? P2PZC_CTR_RECV : P2PZC_CTR_SEND, zcRows ? peer : 0);
   uint64_t seq = valid ? *ctrWord : 0;
   uint64_t q = LL && valid ? *llCtrWord : 0;  // LL messages of this pair-channel so far
+  uint64_t qz = zcRows ? *zcCtrWord : 0;      // RDV messages of this pair-channel so far
   __syncthreads();
   if (!valid) return;
   const uint64_t slice = p2pSliceBytes(dc.slotBytes);
@@ -2049,7 +2078,7 @@ __device__ __forceinline__ void p2pRun(const P2pArgs<S, M>& a, P2pShared& sh) {
     if (c >= (int)msg.nch) continue;
     char* const user = (char*)msg.ptr;
     if constexpr (LL) {
-      if (msg.ll) {
+      if (msg.ll == P2P_LL) {
         // (the host tags no message LL beyond the line area's channels or a slot's lines: its grid check refuses them)
         if (c >= dc.p2pLLChannels || msg.part * 16 > dc.p2pLLLineBytes) break;
         uint64_t lo, hi;
@@ -2093,49 +2122,121 @@ __device__ __forceinline__ void p2pRun(const P2pArgs<S, M>& a, P2pShared& sh) {
         continue;
       }
     }
-    const bool aligned = (msg.ptr & 15) == 0 && !a.elementwise;  // this side's buffer only: staging is always aligned
-    const int nSteps = p2pSteps(msg.bytes, msg.part, slice, c);
-    for (int s = 0; ok && s < nSteps; s++) {
-      uint64_t lo, hi;
-      sliceBounds(msg.part, slice, c, s, msg.bytes, lo, hi);
-      const int slot = (int)(seq % (uint64_t)nSlots);
-      if (tid == 0) {
-        // send: the slot is free once the peer acked slice seq - nSlots; recv: slice seq has arrived
-        sh.want[peer] = recv ? seq + 1 : (seq + 1 > (uint64_t)nSlots ? seq + 1 - nSlots : 0);
-        sh.sigPtr[0] = peerFlag;
-        sh.sigVal[0] = seq + 1;
-      }
-      __syncthreads();
-      if (recv) {
-        ok = waitAll(dc, sh.st, myFlags, sh.want, !noAcq);
+    bool rdv = false, direct = false;  // an RDV message: the done handshake closes it, after the direct copy or the staged loop
+    if constexpr (ZC) {
+      if (msg.ll == P2P_RDV) {
+        if (!zcRows) break;  // (refused by the host's grid check)
+        rdv = true;
+        const uint32_t flag = (uint32_t)(qz + 1) ? (uint32_t)(qz + 1) : 1u;
+        if (tid == 0) {
+          sh.zcMode = 0;
+          if (recv) {
+            const uint64_t d = z->desc[(int)sd.msgOff + m];
+            storeRemote((char*)dc.flags[peer] + p2pZcDescOffset(z->zcOffset, c, me),
+                        u32x4{(uint32_t)d, flag, (uint32_t)(d >> 32), flag});
+            sh.zcMode = p2pZcSerial(d) != 0;
+          } else {
+            u32x4 v;
+            if (llPollLine(dc, (const char*)dc.flags[me] + p2pZcDescOffset(z->zcOffset, c, peer), flag, false, clockTicks(),
+                           sh.st.abort, v)) {
+              const uint64_t d = llPayload(v);
+              const uint32_t serial = p2pZcSerial(d);
+              if (serial != 0) {
+                // this rank's record of the same collective registration: the peer's base and size as mapped here
+                const int slot = (int)(serial % kP2pZcWindows);
+                const ncclWindow_vidmem* w = z->table->serial[slot] == serial ? z->table->win[slot] : nullptr;
+                const uint64_t off = p2pZcOffset(d);
+                if (w == nullptr || w->peerPtr[peer] == nullptr || off > w->peerSize[peer] || msg.bytes > w->peerSize[peer] - off) {
+                  reportError(dc, DERR_WINDOW);
+                  sh.st.abort = 1;
+                } else {
+                  sh.zcDst = w->peerPtr[peer] + off;
+                  sh.zcMode = 1;
+                }
+              }
+            }
+          }
+        }
+        __syncthreads();
+        ok = sh.st.abort == 0;
         if (!ok) break;
-        copyRange<uint8_t, false>(user + lo, dc.staging[me] + stagingOffset(dc, c, STG_RS, slot, peer), hi - lo, aligned);
-        signalAll(sh.sigPtr, sh.sigVal, 1, forceRel);  // credit only: the slot's loads have completed
-      } else {
-        ok = waitAll(dc, sh.st, myFlags, sh.want, forceAcq);
-        if (!ok) break;
-        copyRange<uint8_t, true>(dc.staging[peer] + stagingOffset(dc, c, STG_RS, slot, me), user + lo, hi - lo, aligned);
-        signalAll(sh.sigPtr, sh.sigVal, 1, !noRel);
+        direct = sh.zcMode != 0;
+        if (direct && !recv) {
+          uint64_t lo, hi;
+          sliceBounds(msg.part, msg.part, c, 0, msg.bytes, lo, hi);  // part c: a multiple of 16 bytes from the start
+          char* const dst = sh.zcDst;
+          const bool aligned = ((msg.ptr | (uint64_t)(uintptr_t)dst) & 15) == 0 && !a.elementwise;
+          copyRange<uint8_t, true>(dst + lo, user + lo, hi - lo, aligned);
+        }
       }
-      seq++;
-      __syncthreads();
+    }
+    if (!direct) {
+      const bool aligned = (msg.ptr & 15) == 0 && !a.elementwise;  // this side's buffer only: staging is always aligned
+      const int nSteps = p2pSteps(msg.bytes, msg.part, slice, c);
+      for (int s = 0; ok && s < nSteps; s++) {
+        uint64_t lo, hi;
+        sliceBounds(msg.part, slice, c, s, msg.bytes, lo, hi);
+        const int slot = (int)(seq % (uint64_t)nSlots);
+        if (tid == 0) {
+          // send: the slot is free once the peer acked slice seq - nSlots; recv: slice seq has arrived
+          sh.want[peer] = recv ? seq + 1 : (seq + 1 > (uint64_t)nSlots ? seq + 1 - nSlots : 0);
+          sh.sigPtr[0] = peerFlag;
+          sh.sigVal[0] = seq + 1;
+        }
+        __syncthreads();
+        if (recv) {
+          ok = waitAll(dc, sh.st, myFlags, sh.want, !noAcq);
+          if (!ok) break;
+          copyRange<uint8_t, false>(user + lo, dc.staging[me] + stagingOffset(dc, c, STG_RS, slot, peer), hi - lo, aligned);
+          signalAll(sh.sigPtr, sh.sigVal, 1, forceRel);  // credit only: the slot's loads have completed
+        } else {
+          ok = waitAll(dc, sh.st, myFlags, sh.want, forceAcq);
+          if (!ok) break;
+          copyRange<uint8_t, true>(dc.staging[peer] + stagingOffset(dc, c, STG_RS, slot, me), user + lo, hi - lo, aligned);
+          signalAll(sh.sigPtr, sh.sigVal, 1, !noRel);
+        }
+        seq++;
+        __syncthreads();
+      }
+    }
+    if constexpr (ZC) {
+      if (rdv && ok) {
+        // done: the sender publishes the payload (direct) or merely closes the message (fallback: the staged loop's
+        // flags published it); the receiver waits for it before it writes the pair-channel's next descriptor line
+        if (tid == 0) {
+          sh.want[peer] = qz + 1;
+          sh.sigPtr[0] = (uint64_t*)((char*)dc.flags[peer] + p2pZcDoneOffset(z->zcOffset, c, me));
+          sh.sigVal[0] = qz + 1;
+        }
+        __syncthreads();
+        if (recv) ok = waitAll(dc, sh.st, (const uint64_t*)((const char*)dc.flags[me] + p2pZcDoneOffset(z->zcOffset, c, 0)), sh.want, !noAcq);
+        else signalAll(sh.sigPtr, sh.sigVal, 1, !noRel);
+        qz++;
+        __syncthreads();
+      }
     }
   }
   if (tid == 0) {
     *ctrWord = seq;
     if (LL) *llCtrWord = q;
+    if (zcRows) *zcCtrWord = qz;
   }
 }
 
 template <int S, int M>
 __global__ void __launch_bounds__(kThreads) kCoResident p2pKernel(P2pArgs<S, M> a) {
   __shared__ P2pShared sh;
-  p2pRun<S, M, false>(a, sh);
+  p2pRun<S, M, false, false>(a, nullptr, sh);
 }
 template <int S, int M>
 __global__ void __launch_bounds__(kThreads) kCoResident p2pLLKernel(P2pArgs<S, M> a) {
   __shared__ P2pShared sh;
-  p2pRun<S, M, true>(a, sh);
+  p2pRun<S, M, true, false>(a, nullptr, sh);
+}
+template <int S, int M>
+__global__ void __launch_bounds__(kThreads) kCoResident p2pZcKernel(P2pZcArgs<S, M> a) {
+  __shared__ P2pShared sh;
+  p2pRun<S, M, true, true>(a.p, &a.z, sh);
 }
 
 template <int P>
@@ -2770,29 +2871,57 @@ inline ncclResult_t launchBcast(const LaunchPlan& p) {
   return ncclSuccess;
 }
 
-// One p2pKernel launch — p2pLLKernel iff the launch holds an LL message — with the smallest argument block that holds
-// it (a template only so that the one unit that calls it, kern_gather.hip, instantiates the kernels)
+// One p2pKernel launch — p2pLLKernel iff the launch holds an LL message, p2pZcKernel iff it holds an RDV message (with
+// or without LL ones) — with the smallest argument block that holds it (a template only so that the one unit that calls
+// it, kern_gather.hip, instantiates the kernels)
 template <int S, int M>
-inline void launchP2pArgs(const ncclComm* comm, const P2pLaunch& l, hipStream_t stream, bool ll) {
-  P2pArgs<S, M> a;
-  __builtin_memset(&a, 0, sizeof(a));
+inline void fillP2pArgs(P2pArgs<S, M>& a, const ncclComm* comm, const P2pLaunch& l) {
   a.comm = comm->devComm;
   a.nStreams = (int)l.streams.size();
   a.protoFlags = comm->tune.protoFlags;
   a.elementwise = comm->tune.forceElementwise;
   for (size_t i = 0; i < l.streams.size(); i++) a.st[i] = l.streams[i];
   for (size_t i = 0; i < l.msgs.size(); i++) a.msg[i] = l.msgs[i];
+}
+template <int S, int M>
+inline void launchP2pArgs(const ncclComm* comm, const P2pLaunch& l, hipStream_t stream, bool ll) {
+  P2pArgs<S, M> a;
+  __builtin_memset(&a, 0, sizeof(a));
+  fillP2pArgs(a, comm, l);
   if (ll) NCCL_AMD_LAUNCH((p2pLLKernel<S, M>), dim3(l.grid), dim3(kThreads), 0, stream, a);
   else NCCL_AMD_LAUNCH((p2pKernel<S, M>), dim3(l.grid), dim3(kThreads), 0, stream, a);
+}
+template <int S, int M>
+inline void launchP2pZcArgs(const ncclComm* comm, const P2pLaunch& l, hipStream_t stream) {
+  P2pZcArgs<S, M> a;
+  __builtin_memset(&a, 0, sizeof(a));
+  fillP2pArgs(a.p, comm, l);
+  a.z.table = comm->p2pZcTableDev;
+  a.z.zcOffset = comm->p2pZcOffset;
+  a.z.zcChannels = comm->p2pZcChannels;
+  for (size_t i = 0; i < l.descs.size(); i++) a.z.desc[i] = l.descs[i];
+  NCCL_AMD_LAUNCH((p2pZcKernel<S, M>), dim3(l.grid), dim3(kThreads), 0, stream, a);
 }
 template <int SMALL = 2>
 inline ncclResult_t launchP2pT(const ncclComm* comm, const P2pLaunch& l, hipStream_t stream) {
   if (l.streams.size() > (size_t)kP2pMaxStreams || l.msgs.size() > (size_t)kP2pMaxMsgs || l.grid < 1) return ncclInternalError;
-  bool ll = false;
-  for (const P2pMsg& m : l.msgs) ll = ll || m.ll != 0;
+  bool ll = false, rdv = false;
+  for (const P2pMsg& m : l.msgs) {
+    ll = ll || m.ll == P2P_LL;
+    rdv = rdv || m.ll == P2P_RDV;
+  }
   if (ll && comm->p2pLLChannels < 1) return ncclInternalError;
-  if (l.streams.size() <= (size_t)SMALL && l.msgs.size() <= (size_t)SMALL) launchP2pArgs<SMALL, SMALL>(comm, l, stream, ll);
-  else launchP2pArgs<kP2pMaxStreams, kP2pMaxMsgs>(comm, l, stream, ll);
+  const bool small = l.streams.size() <= (size_t)SMALL && l.msgs.size() <= (size_t)SMALL;
+  if (rdv) {
+    if (comm->p2pZcChannels < 1 || !comm->p2pZcTableDev || l.msgs.size() > (size_t)kP2pZcMaxMsgs || l.descs.size() != l.msgs.size())
+      return ncclInternalError;
+    if (small) launchP2pZcArgs<SMALL, SMALL>(comm, l, stream);
+    else launchP2pZcArgs<kP2pMaxStreams, kP2pZcMaxMsgs>(comm, l, stream);
+  } else if (small) {
+    launchP2pArgs<SMALL, SMALL>(comm, l, stream, ll);
+  } else {
+    launchP2pArgs<kP2pMaxStreams, kP2pMaxMsgs>(comm, l, stream, ll);
+  }
   HIPCHECK(hipGetLastError());
   return ncclSuccess;
 }

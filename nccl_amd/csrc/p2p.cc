@@ -19,6 +19,13 @@
 // too, so both ends tag it alike. A launch that holds an LL message runs p2pLLKernel, any other p2pKernel as before;
 // LL and staged messages of a pair keep separate sequences, each matching in issue order within its kind.
 //
+// A message of at least NCCL_AMD_P2P_ZC_BYTES that is not LL is tagged RDV (device_abi.h p2pKindOf), again from its byte
+// count and rank-0 constants alone, and keeps the staged cut. The RECEIVING side alone looks its recvbuff up in the
+// communicator's window table: inside a live window the message's descriptor names that window's registration serial
+// and the offset, and the sender stores the payload straight there; outside (or straddling the window's end) the
+// descriptor's serial is 0 and both ends run the staged loop for it. A launch that holds an RDV message runs
+// p2pZcKernel, whose argument block carries the descriptors and therefore at most kP2pZcMaxMsgs messages.
+//
 // ncclAlltoAll / ncclGather whose sendbuff lies in a symmetric window do not expand: they are planned and launched as
 // one collective on the zero-copy kernel (symA2ASubmit below, enqueue.cc planSymA2A).
 #include <string.h>
@@ -47,20 +54,39 @@ static P2pCut p2pLLCutFor(const ncclComm* comm, size_t bytes) {
   return p2pLLCut(bytes, (uint64_t)comm->p2pLLLineBytes, comm->p2pLLChannels);
 }
 
+// The descriptor of a received RDV message: the window (of any flag: every window is a put target) that holds
+// [buff, buff + bytes) wholly and is still in the table, as its serial and the offset inside it; 0: none, it is staged.
+static uint64_t p2pZcDescFor(const ncclComm* comm, const void* buff, size_t bytes) {
+  const P2pZcWinTable* t = comm->p2pZcTable;
+  const uintptr_t a = (uintptr_t)buff;
+  for (int s = 0; t && s < kP2pZcWindows; s++) {
+    const ncclWindow_vidmem* w = t->win[s];
+    if (t->serial[s] == 0 || w == nullptr || w->comm != comm) continue;
+    const uintptr_t b = (uintptr_t)w->userPtr;
+    if (a >= b && bytes <= w->size && a - b <= w->size - bytes && a - b <= kP2pZcOffsetMax) return p2pZcPack(t->serial[s], a - b);
+  }
+  return 0;
+}
+
 ncclResult_t p2pPlan(ncclComm* comm, const std::vector<P2pOp>& ops, P2pPlan* plan) {
   const int n = comm->nRanks, me = comm->rank;
   plan->self.clear();
   plan->launches.clear();
   plan->maxPeerBytes = 0;
   std::vector<P2pMsg> sendTo[NCCL_AMD_MAX_RANKS], recvFrom[NCCL_AMD_MAX_RANKS];
+  std::vector<uint64_t> recvDesc[NCCL_AMD_MAX_RANKS];  // beside recvFrom, once a peer's list holds an RDV message
   bool remote = false;
   for (const P2pOp& op : ops) {
     if (op.peer < 0 || op.peer >= n) return ncclInternalError;  // (checked at the entry point)
     if (op.bytes == 0) continue;  // both sides know: counts match. No handshake, no place in the order
     P2pCut cut = p2pLLCutFor(comm, op.bytes);
-    const uint32_t ll = cut.nch > 0;
-    if (!ll) cut = p2pCutFor(comm, op.bytes);
+    const uint32_t ll = (uint32_t)p2pKindOf(op.bytes, cut.nch > 0, comm->p2pZcChannels > 0 ? (uint64_t)comm->tune.p2pZcBytes : 0);
+    if (ll != P2P_LL) cut = p2pCutFor(comm, op.bytes);
     (op.recv ? recvFrom : sendTo)[op.peer].push_back({(uint64_t)(uintptr_t)op.buff, (uint64_t)op.bytes, cut.part, (uint32_t)cut.nch, ll});
+    if (op.recv && ll == P2P_RDV && op.peer != me) {
+      recvDesc[op.peer].resize(recvFrom[op.peer].size(), 0);
+      recvDesc[op.peer].back() = p2pZcDescFor(comm, op.buff, op.bytes);
+    }
     remote = remote || op.peer != me;
   }
   // round 0: self sends and recvs pair up in issue order (reference enqueue.cc:1158-1166)
@@ -92,6 +118,8 @@ ncclResult_t p2pPlan(ncclComm* comm, const std::vector<P2pOp>& ops, P2pPlan* pla
     cur.grid = 0;
     cur.streams.clear();
     cur.msgs.clear();
+    cur.descs.clear();
+    cur.nRdv = 0;
   };
   for (int r = 1; r < n; r++) {
     const int peers[2] = {(me + r) % n, (me - r + n) % n};
@@ -107,14 +135,19 @@ ncclResult_t p2pPlan(ncclComm* comm, const std::vector<P2pOp>& ops, P2pPlan* pla
     const int need = nch[0] + nch[1];
     const size_t needMsgs = lists[0]->size() + lists[1]->size();
     if (need == 0) continue;
-    if (need > budget || needMsgs > (size_t)kP2pMaxMsgs) {
+    // a launch that holds an RDV message carries the descriptors too: fewer messages fit (device_abi.h P2pZcArgs)
+    int rdv = 0;
+    for (int d = 0; d < 2; d++)
+      for (const P2pMsg& m : *lists[d]) rdv += m.ll == P2P_RDV;
+    const size_t roundCap = rdv ? kP2pZcMaxMsgs : kP2pMaxMsgs, curCap = rdv || cur.nRdv ? kP2pZcMaxMsgs : kP2pMaxMsgs;
+    if (need > budget || needMsgs > roundCap) {
       WARN("ncclGroupEnd: round %d of rank %d (send to %d, recv from %d) needs %d workgroups and %zu message descriptors "
-           "in one launch; at most %d and %d fit", r, me, peers[0], peers[1], need, needMsgs, budget, kP2pMaxMsgs);
+           "in one launch; at most %d and %zu fit", r, me, peers[0], peers[1], need, needMsgs, budget, roundCap);
       return ncclInvalidUsage;
     }
-    if (cur.grid + need > budget || cur.msgs.size() + needMsgs > (size_t)kP2pMaxMsgs ||
-        cur.streams.size() + 2 > (size_t)kP2pMaxStreams)
+    if (cur.grid + need > budget || cur.msgs.size() + needMsgs > curCap || cur.streams.size() + 2 > (size_t)kP2pMaxStreams)
       close();
+    cur.nRdv += rdv;
     if (cur.grid == 0) cur.firstRound = r;
     cur.lastRound = r;
     for (int d = 0; d < 2; d++) {
@@ -129,6 +162,10 @@ ncclResult_t p2pPlan(ncclComm* comm, const std::vector<P2pOp>& ops, P2pPlan* pla
       s.recv = (uint8_t)d;
       cur.streams.push_back(s);
       cur.msgs.insert(cur.msgs.end(), lists[d]->begin(), lists[d]->end());
+      if (cur.nRdv) {  // msgs[i]'s descriptor at descs[i]: the received RDV messages' planned ones, 0 everywhere else
+        cur.descs.resize(cur.msgs.size(), 0);
+        if (d == 1) std::copy(recvDesc[peers[1]].begin(), recvDesc[peers[1]].end(), cur.descs.end() - (ptrdiff_t)lists[1]->size());
+      }
       cur.grid += nch[d];
     }
   }
@@ -151,8 +188,14 @@ static ncclResult_t p2pCheckGrid(const ncclComm* comm, const P2pLaunch& l) {
            s.peer != comm->rank;
     for (size_t k = 0; good && k < s.nMsgs; k++) {
       good = moff + k < l.msgs.size() && l.msgs[moff + k].nch <= s.nch;
-      if (good && l.msgs[moff + k].ll)
+      if (good && l.msgs[moff + k].ll == P2P_LL)
         good = (int)l.msgs[moff + k].nch <= comm->p2pLLChannels && l.msgs[moff + k].part * 16 <= comm->p2pLLLineBytes;
+      // an RDV message's within the RDV area's channels (its descriptor lines, done words and counter rows); the launch
+      // then carries one descriptor per message, within the smaller cap, and the window table exists
+      if (good && l.msgs[moff + k].ll == P2P_RDV)
+        good = (int)l.msgs[moff + k].nch <= comm->p2pZcChannels && comm->p2pZcTable != nullptr &&
+               l.msgs.size() <= (size_t)kP2pZcMaxMsgs && l.descs.size() == l.msgs.size();
+      if (good && l.msgs[moff + k].ll > P2P_RDV) good = false;
     }
     off += s.nch;
     moff += s.nMsgs;
@@ -170,7 +213,18 @@ ncclResult_t p2pLaunchPlan(ncclComm* comm, const P2pPlan& plan, hipStream_t stre
   for (const P2pLaunch& l : plan.launches) {
     TRACE("p2p launch: rank %d rounds %d..%d, %zu streams, %zu messages, %d workgroups", comm->rank, l.firstRound,
           l.lastRound, l.streams.size(), l.msgs.size(), l.grid);
-    const size_t nLL = std::count_if(l.msgs.begin(), l.msgs.end(), [](const P2pMsg& m) { return m.ll != 0; });
+    const size_t nLL = std::count_if(l.msgs.begin(), l.msgs.end(), [](const P2pMsg& m) { return m.ll == P2P_LL; });
+    if (l.nRdv) {
+      size_t nRecv = 0, nDirect = 0;
+      for (const P2pStream& s : l.streams)
+        for (size_t k = 0; s.recv && k < s.nMsgs; k++)
+          if (l.msgs[s.msgOff + k].ll == P2P_RDV) {
+            nRecv++;
+            nDirect += p2pZcSerial(l.descs[s.msgOff + k]) != 0;
+          }
+      TRACE("p2p launch: rank %d rounds %d..%d, rdv messages %d (received: %zu direct, %zu fell back)", comm->rank,
+            l.firstRound, l.lastRound, l.nRdv, nDirect, nRecv - nDirect);
+    }
     if (nLL) TRACE("p2p launch: rank %d rounds %d..%d, ll messages %zu", comm->rank, l.firstRound, l.lastRound, nLL);
     NCCLCHECK(launchP2pKernel(comm, l, stream));
   }

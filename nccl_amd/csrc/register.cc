@@ -179,11 +179,29 @@ ncclResult_t windowRegister(ncclComm* comm, void* buff, size_t size, ncclWindow_
   }
   comm->windows.push_back(w);
   *win = w;
+  // The registration serial: every rank counts the registrations that succeeded, and they succeed or fail together, so
+  // a serial names the same window on every rank. With the RDV protocol of ncclSend / ncclRecv on, the window enters the
+  // table its senders resolve a receiver's descriptor in (device_abi.h P2pZcWinTable), taking its slot from whatever
+  // window held it: that one's recvbuffs fall back to the staged path from now on.
+  comm->winSerial = p2pZcNextSerial(comm->winSerial);
+  if (comm->p2pZcTable) {
+    P2pZcWinTable* t = comm->p2pZcTable;
+    const int slot = (int)(comm->winSerial % kP2pZcWindows);
+    __atomic_store_n(&t->serial[slot], 0u, __ATOMIC_RELEASE);
+    t->win[slot] = w;
+    __atomic_store_n(&t->serial[slot], comm->winSerial, __ATOMIC_RELEASE);
+  }
   INFO("rank %d: window %p size %zu flags %d registered", comm->rank, buff, size, w->flags);
   return ncclSuccess;
 }
 
 static void windowRelease(ncclComm* comm, ncclWindow_vidmem* w) {
+  if (comm->p2pZcTable)  // no RDV descriptor names it any more (p2p.cc looks recvbuffs up in the table alone)
+    for (int s = 0; s < kP2pZcWindows; s++)
+      if (comm->p2pZcTable->win[s] == w) {
+        comm->p2pZcTable->serial[s] = 0;
+        comm->p2pZcTable->win[s] = nullptr;
+      }
   for (int r = 0; r < comm->nRanks; r++)
     if (w->peerBase[r]) ipcUnmap(comm, r, w->peerBase[r]);
   (void)hipHostFree(w);

@@ -36,8 +36,11 @@ static size_t p2pLLOffset(const ncclComm* c) {
 static size_t p2pLLBytes(const ncclComm* c) {
   return (size_t)c->p2pLLChannels * kP2pLLDepth * c->nRanks * c->p2pLLLineBytes;
 }
+// then the p2p RDV area (device_abi.h; empty unless NCCL_AMD_P2P_ZC_BYTES is set: the layout is then the one without it)
+static size_t p2pZcOffset(const ncclComm* c) { return (p2pLLOffset(c) + p2pLLBytes(c) + 255) / 256 * 256; }
+static size_t p2pZcBytes(const ncclComm* c) { return (size_t)c->p2pZcChannels * kP2pZcChannelBytes; }
 // then the mapping-check area (mapcheck.cc): 2 rows x NCCL_AMD_MAX_RANKS x 16 bytes, used once at init
-static size_t probeOffset(const ncclComm* c) { return (p2pLLOffset(c) + p2pLLBytes(c) + 255) / 256 * 256; }
+static size_t probeOffset(const ncclComm* c) { return (p2pZcOffset(c) + p2pZcBytes(c) + 255) / 256 * 256; }
 static size_t flagsBytes(const ncclComm* c) { return probeOffset(c) + kMapProbeBytes; }
 
 // Device memory this communicator holds on its GPU (ncclCommMemStats): staging slab, flag/LL lines,
@@ -76,6 +79,12 @@ ncclResult_t transportSetup(ncclComm* comm) {
     comm->p2pLLChannels = std::min(comm->tune.p2pLLNch, comm->maxChannels);
     comm->p2pLLLineBytes = (size_t)comm->tune.p2pLLLineBytes;
   }
+  // the RDV area likewise: one descriptor line and one done word per channel and peer, on the channels a message can be
+  // cut into (p2pCut's: the RDV cut is the staged one); its offset is fixed here, before any channel count is lowered
+  if (comm->tune.p2pZcBytes > 0) {
+    comm->p2pZcChannels = std::max(1, std::min(comm->tune.p2pMaxCh, comm->maxChannels));
+    comm->p2pZcOffset = p2pZcOffset(comm);
+  }
   size_t sb = stagingBytes(comm), fb = flagsBytes(comm);
   {
     // only the allocations themselves are serialized with imports / releases (gMapMu): the fd server thread
@@ -98,6 +107,9 @@ ncclResult_t transportSetup(ncclComm* comm) {
   if (comm->p2pLLChannels > 0)
     INFO("rank %d dev %d: p2p LL lines %zu KiB (%d ch x %d slots x %d ranks x %zu B)", comm->rank, comm->device,
          p2pLLBytes(comm) >> 10, comm->p2pLLChannels, kP2pLLDepth, comm->nRanks, comm->p2pLLLineBytes);
+  if (comm->p2pZcChannels > 0)
+    INFO("rank %d dev %d: p2p RDV area %zu KiB (%d ch x %zu B)", comm->rank, comm->device, p2pZcBytes(comm) >> 10,
+         comm->p2pZcChannels, (size_t)kP2pZcChannelBytes);
   return ncclSuccess;
 }
 
@@ -186,13 +198,15 @@ ncclResult_t transportRemapPeer(ncclComm* comm, int r) {
 // freed memory. Returns ncclSuccess or ncclTimeout; the caller frees either way.
 ncclResult_t transportDrainCredits(ncclComm* comm) {
   if (comm->nRanks == 1 || !comm->counters || !comm->flags) return ncclSuccess;
-  const size_t nc = (size_t)comm->maxChannels * CTR_KINDS * NCCL_AMD_MAX_RANKS;
+  const size_t nc = comm->countersAllocBytes / sizeof(uint64_t);  // (with the RDV rows, where there are any)
   const size_t nf = flagWordBytes(comm) / sizeof(uint64_t);
-  std::vector<uint64_t> ctr(nc), flg(nf);
+  std::vector<uint64_t> ctr(nc), flg(nf), zcDone(p2pZcBytes(comm) / sizeof(uint64_t));
   HIPCHECK(hipMemcpy(ctr.data(), comm->counters, nc * sizeof(uint64_t), hipMemcpyDeviceToHost));
   const int64_t limitMs = paramInt("NCCL_AMD_DESTROY_TIMEOUT_MS", 10000);
   for (int64_t waited = 0;; waited++) {
     HIPCHECK(hipMemcpy(flg.data(), comm->flags, nf * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (!zcDone.empty())
+      HIPCHECK(hipMemcpy(zcDone.data(), (char*)comm->flags + comm->p2pZcOffset, zcDone.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     bool done = true;
     for (int c = 0; c < comm->maxChannels && done; c++)
       for (int p = 0; p < comm->nRanks && done; p++) {
@@ -201,6 +215,10 @@ ncclResult_t transportDrainCredits(ncclComm* comm) {
                flg[flagIndex(c, FLG_AG_ACK, p)] >= ctr[ctrIndex(c, CTR_SEND_AG, p)] &&
                flg[flagIndex(c, FLG_PULL_ACK, p)] >= ctr[ctrIndex(c, CTR_PULL_PUB, 0)] &&
                flg[flagIndex(c, FLG_P2PLL_ACK, p)] >= ctr[ctrIndex(c, CTR_P2PLL_SEND, p)];
+        // ... and the done flag of every RDV message received from p (the sender's last store of a message)
+        if (done && c < comm->p2pZcChannels)
+          done = zcDone[((size_t)c * kP2pZcChannelBytes + NCCL_AMD_MAX_RANKS * 16) / 8 + p] >=
+                 ctr[p2pZcCtrIndex(comm->maxChannels, c, P2PZC_CTR_RECV, p)];
       }
     if (done) return ncclSuccess;
     if (waited >= limitMs) {
@@ -226,6 +244,9 @@ ncclResult_t transportFree(ncclComm* comm) {
   if (comm->devComm) (void)hipFree(comm->devComm);
   if (comm->hostAbort) (void)hipHostFree(comm->hostAbort);
   if (comm->hostError) (void)hipHostFree(comm->hostError);
+  if (comm->p2pZcTable) (void)hipHostFree(comm->p2pZcTable);
+  comm->p2pZcTable = nullptr;
+  comm->p2pZcTableDev = nullptr;
   comm->staging = nullptr;
   comm->flags = nullptr;
   comm->counters = nullptr;
@@ -238,6 +259,8 @@ ncclResult_t transportFree(ncclComm* comm) {
 ncclResult_t commAllocDevState(ncclComm* comm) {
   HIPCHECK(hipSetDevice(comm->device));
   size_t cb = (size_t)comm->maxChannels * CTR_KINDS * NCCL_AMD_MAX_RANKS * sizeof(uint64_t);
+  // the RDV sequences behind the block (device_abi.h p2pZcCtrIndex), only where the RDV area was allocated
+  cb += (size_t)comm->p2pZcChannels * P2PZC_CTR_KINDS * NCCL_AMD_MAX_RANKS * sizeof(uint64_t);
   HIPCHECK(hipMalloc((void**)&comm->counters, cb));
   comm->countersAllocBytes = cb;
   HIPCHECK(hipMemset(comm->counters, 0, cb));
@@ -279,6 +302,15 @@ ncclResult_t commAllocDevState(ncclComm* comm) {
   if (comm->p2pLLChannels > comm->chanCap / 2) comm->p2pLLChannels = comm->chanCap / 2;
   d.p2pLLLineBytes = comm->p2pLLLineBytes;
   d.p2pLLChannels = comm->p2pLLChannels;
+  // the RDV area too (its rows were allocated above for the full count), and the window table its senders read
+  if (comm->p2pZcChannels > 0) {
+    comm->p2pZcChannels = std::max(1, std::min(comm->p2pZcChannels, comm->chanCap / 2));
+    HIPCHECK(hipHostMalloc((void**)&comm->p2pZcTable, sizeof(P2pZcWinTable), hipHostMallocMapped | hipHostMallocPortable));
+    memset(comm->p2pZcTable, 0, sizeof(P2pZcWinTable));
+    void* dTable = nullptr;
+    HIPCHECK(hipHostGetDevicePointer(&dTable, comm->p2pZcTable, 0));
+    comm->p2pZcTableDev = (const P2pZcWinTable*)dTable;
+  }
   void* dAbort = nullptr;
   void* dErr = nullptr;
   HIPCHECK(hipHostGetDevicePointer(&dAbort, comm->hostAbort, 0));

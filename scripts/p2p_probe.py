@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""One-GPU probe of the staged ncclSend / ncclRecv path beside a device-to-device hipMemcpyAsync of the same bytes.
+"""One-GPU probe of the staged and the RDV (zero-copy rendezvous) ncclSend / ncclRecv paths beside a device-to-device
+hipMemcpyAsync of the same bytes.
 
   p2p_probe.py [--warmup 5] [--iters 10] [--rounds 3] [--step-timeout 240] [--out FILE.json]
 
@@ -10,7 +11,9 @@ ends the probe, nothing further is started on the GPU):
 Ranks are comms of one process on GPU 0 (NCCL_MULTI_RANK_GPU_ENABLE=1). A call's time is the slowest rank's HIP event
 pair around it. The yardstick, timed in alternation with it in the same rounds: every rank copies the bytes it sends
 with one hipMemcpyAsync (device to device) on its own stream. The staged path copies every byte twice (into the
-peer's staging slot, out of it), so about twice the yardstick is its floor on one GPU. No byte crosses an xGMI link
+peer's staging slot, out of it), so about twice the yardstick is its floor on one GPU. The RDV column runs the same
+calls, in the same rounds, on a second set of communicators made under NCCL_AMD_P2P_ZC_BYTES with the recvbuffs
+registered as windows: one copy per byte. No byte crosses an xGMI link
 here: the figures are HBM-bound rehearsal records and say nothing about link speed."""
 import argparse
 import ctypes
@@ -37,10 +40,15 @@ def run_step(step, a):
     hip = ctypes.CDLL("libamdhip64.so", mode=ctypes.RTLD_GLOBAL)
     hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
     comms = nccl_amd.Communicator.init_all([0] * n)
+    os.environ["NCCL_AMD_P2P_ZC_BYTES"] = str(1 << 20)
+    comms_zc = nccl_amd.Communicator.init_all([0] * n)
+    del os.environ["NCCL_AMD_P2P_ZC_BYTES"]
     streams = [torch.cuda.Stream() for _ in range(n)]
     g = torch.Generator(device="cuda").manual_seed(1)
     send = [torch.randint(0, 256, (nbytes,), dtype=torch.uint8, device="cuda", generator=g) for _ in range(n)]
     recv = [torch.zeros(nbytes, dtype=torch.uint8, device="cuda") for _ in range(n)]
+    with nccl_amd.group():
+        wins = [comms_zc[r].register_window(recv[r].data_ptr(), nbytes, 0) for r in range(n)]
 
     def call(kind):
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
@@ -51,41 +59,52 @@ def run_step(step, a):
                 rc = hip.hipMemcpyAsync(recv[r].data_ptr(), send[r].data_ptr(), nbytes, 3, streams[r].cuda_stream)
                 assert rc == 0, f"hipMemcpyAsync returned {rc}"
         else:
+            cs = comms_zc if kind == "rdv" else comms
             with nccl_amd.group():
                 for r in range(n):
                     if step == "exchange":
-                        comms[r].send(send[r], 1 - r, stream=streams[r])
-                        comms[r].recv(recv[r], 1 - r, stream=streams[r])
+                        cs[r].send(send[r], 1 - r, stream=streams[r])
+                        cs[r].recv(recv[r], 1 - r, stream=streams[r])
                     else:
-                        comms[r].alltoall(send[r], recv[r], stream=streams[r])
+                        cs[r].alltoall(send[r], recv[r], stream=streams[r])
         for r in range(n):
             ev[r][1].record(streams[r])
         torch.cuda.synchronize()
         return max(s.elapsed_time(e) for s, e in ev)
 
+    blk = nbytes // n
+
+    def match():
+        if step == "exchange":
+            return all(torch.equal(recv[r], send[1 - r]) for r in range(n))
+        return all(torch.equal(recv[r], torch.cat([send[i][r * blk:(r + 1) * blk] for i in range(n)])) for r in range(n))
+
+    ok = True
     for _ in range(a.warmup):
         call("memcpy")
-        call("p2p")
-    blk = nbytes // n
-    if step == "exchange":
-        ok = all(torch.equal(recv[r], send[1 - r]) for r in range(n))
-    else:
-        ok = all(torch.equal(recv[r], torch.cat([send[i][r * blk:(r + 1) * blk] for i in range(n)])) for r in range(n))
+        for kind in ("p2p", "rdv"):
+            for t_ in recv:
+                t_.zero_()
+            call(kind)
+            ok = ok and match()
     rounds = []
     for _ in range(a.rounds):
-        t = {"p2p": [], "memcpy": []}
+        t = {"p2p": [], "rdv": [], "memcpy": []}
         for _ in range(a.iters):
-            for kind in ("p2p", "memcpy"):
+            for kind in t:
                 t[kind].append(call(kind))
         rounds.append({k: {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4),
                            "max_ms": round(max(v), 4)} for k, v in t.items()})
-    errs = [c.async_error() for c in comms]
-    for c in comms:
+    errs = [c.async_error() for c in comms + comms_zc]
+    for r in range(n):
+        comms_zc[r].deregister_window(wins[r])
+    for c in comms + comms_zc:
         c.destroy()
-    mp_, mm = (statistics.median(r[k]["median_ms"] for r in rounds) for k in ("p2p", "memcpy"))
+    mp_, mz, mm = (statistics.median(r[k]["median_ms"] for r in rounds) for k in ("p2p", "rdv", "memcpy"))
     res = {"step": step, "n_ranks": n, "bytes_sent_per_rank": nbytes, "warmup": a.warmup, "iters_per_round": a.iters,
            "timing": "HIP events on every rank's stream around the call, slowest rank", "rounds": rounds,
-           "p2p_median_ms": mp_, "memcpy_median_ms": mm, "p2p_over_memcpy": round(mp_ / mm, 3),
+           "p2p_median_ms": mp_, "rdv_median_ms": mz, "memcpy_median_ms": mm, "p2p_over_memcpy": round(mp_ / mm, 3),
+           "rdv_over_memcpy": round(mz / mm, 3), "rdv_over_p2p": round(mz / mp_, 3),
            "outputs_match": bool(ok), "async_errors": errs, "device": torch.cuda.get_device_name(0)}
     print(json.dumps(res))
     return 0 if ok and not any(errs) else 1
@@ -115,7 +134,7 @@ def main():
             print(f"step {step} failed ({out.returncode}); stopping\n{out.stdout[-2000:]}{out.stderr[-2000:]}", file=sys.stderr)
             return 1
         results.append(json.loads(out.stdout.strip().splitlines()[-1]))
-    res = {"what": "staged send/recv and all-to-all beside hipMemcpyAsync of the same bytes, ranks of one process on one "
+    res = {"what": "staged and RDV send/recv and all-to-all beside hipMemcpyAsync of the same bytes, ranks of one process on one "
                    "GPU (no xGMI link is crossed)", "steps": results}
     print(json.dumps(res))
     if a.out:
