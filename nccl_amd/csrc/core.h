@@ -291,7 +291,8 @@ struct CommTuning {
   int symOneShot;           // NCCL_AMD_SYM_ONESHOT: caller promises out-of-place window AllReduces
   int symWtPublish;         // NCCL_AMD_SYM_WT: symmetric kernels publish with write-through stores, no L2 write-back
   int symWideAcc;           // NCCL_AMD_SYM_WIDE_ACC: zero-copy fp16 / bf16 / fp8 Sum and Avg accumulate in f32, one rounding
-  int localRegister;        // NCCL_LOCAL_REGISTER: ncclCommRegister maps buffers into peers (zero-copy collectives)
+  int wideAcc;              // NCCL_AMD_WIDE_ACC: that (it sets symWideAcc) and the same fold on the direct, one-shot and LL plans
+  int localRegister;       // NCCL_LOCAL_REGISTER: ncclCommRegister maps buffers into peers (zero-copy collectives)
   int graphRegister;        // NCCL_GRAPH_REGISTER: buffers of captured collectives are registered automatically
   int noAggregation;        // NCCL_AMD_NO_AGGREGATION
   int64_t oneShotBytes;     // NCCL_AMD_ONESHOT_BYTES
@@ -518,6 +519,10 @@ struct LaunchPlan {  // one kernel launch (reference: struct ncclKernelPlan, src
   int64_t copyGrid;
   int copyXcdShift;
   int pipeKind;     // ALGO_PIPE: PipeKind (pipe.h)
+  // NCCL_AMD_WIDE_ACC on a plan that folds at one owner (ALGO_DIRECT / ALGO_ONESHOT / ALGO_LL): 1 Sum, 2 Avg of a
+  // 16- / 8-bit float fold in f32 with one rounding (kernels.h foldRangeWide); args.redArg / ll.redArg then hold
+  // the f32 bits of 1.0f / nRanks. Part of the batch key (enqueue.cc sameRedOp)
+  int wide;
 };
 
 ncclResult_t enqueueCheck(CollInfo* info);

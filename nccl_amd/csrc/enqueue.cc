@@ -241,6 +241,11 @@ void loadTuning(CommTuning* t) {
   // symmetric kernels (kernels.h foldRangeWide). 0 (default): the per-hop fold, bit-equal to the ring
   // order of every other path (§6)
   t->symWideAcc = (int)paramInt("NCCL_AMD_SYM_WIDE_ACC", 0) != 0;
+  // NCCL_AMD_WIDE_ACC=1: the same fold on every plan that folds all n contributions at one owner — the zero-copy
+  // kernels (it implies the knob above) and the staged direct, one-shot and LL / LL64 plans (planColl, DESIGN.md
+  // §2.8). NCCL_AMD_SYM_WIDE_ACC alone leaves the staged plans per-hop
+  t->wideAcc = (int)paramInt("NCCL_AMD_WIDE_ACC", 0) != 0;
+  if (t->wideAcc) t->symWideAcc = 1;
   // reference register.cc:16 / enqueue.cc:283 (both default on): ncclCommRegister'd buffers and, under stream
   // capture, the captured collectives' buffers run the zero-copy kernel (register.cc)
   t->localRegister = (int)paramInt("NCCL_LOCAL_REGISTER", 1);
@@ -934,9 +939,26 @@ ncclResult_t planColl(const CollInfo& info, LaunchPlan& p, SymPlan& sp, int* kin
     if (tuned == TUNE_DIRECT) oneShot = false;
   }
   const bool oneShotAR = oneShot;
+  // NCCL_AMD_WIDE_ACC: the built-in Sum and Avg of a 16- / 8-bit float fold in f32 with one rounding on the plans
+  // that fold all n contributions at one owner (LL / LL64, one-shot, direct). From the agreed knob,
+  // the datatype and the op alone — never a pointer or a role — so every rank runs the same kernel. The plan's
+  // operator becomes the wide one: no functor argument, the Avg scale as the f32 bits of 1.0f / n
+  const bool smallFloat = info.datatype == ncclFloat16 || info.datatype == ncclBfloat16 ||
+                          info.datatype == ncclFloat8e4m3 || info.datatype == ncclFloat8e5m2;
+  const int wide = !(comm->tune.wideAcc && smallFloat) || info.func == FUNC_ALLGATHER || info.func == FUNC_BROADCAST ? 0
+                   : info.op == ncclSum ? 1 : info.op == ncclAvg ? 2 : 0;
+  auto markWide = [&]() {
+    const float r = 1.0f / (float)n;
+    p.wide = wide;
+    p.devOp = DEV_SUM;
+    p.args.redArg = 0;
+    memcpy(&p.args.redArg, &r, sizeof(r));
+    p.args.redArgPtr = nullptr;
+  };
   // LL protocol (reference NCCL_PROTO=LL, prims_ll.h): small AllReduce / ReduceScatter / AllGather /
   // Reduce, one launch, no fences
   if (!refOrder && !ringProtoPart && llPlan(info, &p.ll.ops[0])) {
+    if (wide) markWide();
     p.algo = ALGO_LL;
     p.ll.comm = comm->devComm;
     p.ll.counters = comm->counters;
@@ -944,8 +966,9 @@ ncclResult_t planColl(const CollInfo& info, LaunchPlan& p, SymPlan& sp, int* kin
     p.ll.redArgPtr = p.args.redArgPtr;
     p.ll.nOps = 1;
     p.nChannels = p.ll.ops[0].nch;
-    TRACE("%s: %s count %zu nch %d part %lu %s", info.opName, p.ll.ops[0].proto == LLP_LL64 ? "LL128(LL64)" : "LL",
-          count, p.nChannels, (unsigned long)p.ll.ops[0].part, p.ll.ops[0].proto == LLP_LL64 ? "lines" : "payloads");
+    TRACE("%s: %s count %zu nch %d part %lu %s%s", info.opName, p.ll.ops[0].proto == LLP_LL64 ? "LL128(LL64)" : "LL",
+          count, p.nChannels, (unsigned long)p.ll.ops[0].part, p.ll.ops[0].proto == LLP_LL64 ? "lines" : "payloads",
+          wide ? " wide 1" : "");
     return ncclSuccess;
   }
   // The reference's own algorithms, forced with NCCL_ALGO=RING / TREE (pipe.h): the ring for AllReduce,
@@ -1125,8 +1148,6 @@ ncclResult_t planColl(const CollInfo& info, LaunchPlan& p, SymPlan& sp, int* kin
       // agreed knob, the datatype and the op alone, so every rank runs the same kernel. Ops whose argument depends on
       // the datatype (MinMax, user PreMulSum), Prod and every other type keep the per-hop fold, as in the reference
       // (src/device/symmetric/primitives.cuh:239-241)
-      const bool smallFloat = info.datatype == ncclFloat16 || info.datatype == ncclBfloat16 ||
-                              info.datatype == ncclFloat8e4m3 || info.datatype == ncclFloat8e5m2;
       if (comm->tune.symWideAcc && smallFloat && sp.coll != 3 /*SYM_AG*/ && (info.op == ncclSum || info.op == ncclAvg)) {
         sp.args.wide = info.op == ncclAvg ? 2 : 1;
         sp.args.wideScale = 1.0f / (float)n;
@@ -1151,9 +1172,10 @@ ncclResult_t planColl(const CollInfo& info, LaunchPlan& p, SymPlan& sp, int* kin
     if (n >= 3 && comm->tune.linkChannels > 0 && tunedNch == 0) maxCh = std::min(maxCh, comm->tune.linkChannels);
     planChannels(comm, blockElems * ts, ts, p, minPart, maxCh);
   }
-  TRACE("%s: count %zu dt %d op %d -> nch %d part %lu slice %lu steps %d aligned %d", info.opName, count,
+  if (wide) markWide();
+  TRACE("%s: count %zu dt %d op %d -> nch %d part %lu slice %lu steps %d aligned %d%s", info.opName, count,
         (int)info.datatype, (int)info.op, p.nChannels, (unsigned long)p.args.part, (unsigned long)p.args.slice,
-        p.args.nSteps, p.args.aligned);
+        p.args.nSteps, p.args.aligned, wide ? " wide 1" : "");
   return ncclSuccess;
 }
 
@@ -1235,7 +1257,7 @@ void collProgress(ncclComm* comm, hipStream_t stream) {
 // (collBatchKernel). Every rank of a comm issues the same op sequence and plans each op alike, so every
 // rank forms the same batches.
 static bool sameRedOp(const LaunchPlan& a, const LaunchPlan& b) {
-  return a.devOp == b.devOp && a.args.redArg == b.args.redArg && a.args.redArgPtr == b.args.redArgPtr;
+  return a.devOp == b.devOp && a.wide == b.wide && a.args.redArg == b.args.redArg && a.args.redArgPtr == b.args.redArgPtr;
 }
 
 bool batchable(const std::vector<PlannedColl>& run, const PlannedColl& b) {
@@ -1296,6 +1318,7 @@ ncclResult_t launchBatch(std::vector<PlannedColl>& run) {
       if (p.func == FUNC_ALLGATHER && run[k].info.func != FUNC_ALLGATHER) {
         p.func = run[k].info.func;
         p.devOp = run[k].p.devOp;
+        p.wide = run[k].p.wide;
         p.ll.redArg = run[k].p.ll.redArg;
         p.ll.redArgPtr = run[k].p.ll.redArgPtr;
       }

@@ -2,7 +2,7 @@
 #include "kernels.h"
 namespace ncclamd {
 ncclResult_t launchKernBF16(const LaunchPlan& p) {
-  return launchOp<bf16_t>(p);
+  return launchSmallFloatOp<bf16_t>(p);
 }
 // Force this code object to load now (see warmKernels in kernels.hip).
 hipError_t warmKernBF16() {

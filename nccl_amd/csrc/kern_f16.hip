@@ -2,7 +2,7 @@
 #include "kernels.h"
 namespace ncclamd {
 ncclResult_t launchKernF16(const LaunchPlan& p) {
-  return launchOp<half_t>(p);
+  return launchSmallFloatOp<half_t>(p);
 }
 // Force this code object to load now (see warmKernels in kernels.hip).
 hipError_t warmKernF16() {

@@ -2,7 +2,7 @@
 #include "kernels.h"
 namespace ncclamd {
 ncclResult_t launchKernFp8(const LaunchPlan& p) {
-  return p.datatype == ncclFloat8e4m3 ? launchOp<e4m3_t>(p) : launchOp<e5m2_t>(p);
+  return p.datatype == ncclFloat8e4m3 ? launchSmallFloatOp<e4m3_t>(p) : launchSmallFloatOp<e5m2_t>(p);
 }
 // Force this code object to load now (see warmKernels in kernels.hip).
 hipError_t warmKernFp8() {

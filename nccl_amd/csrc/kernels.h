@@ -723,11 +723,33 @@ struct Wide {
   }
 };
 
-template <typename T, bool AVG>
+// The wide operators outside symKernel (collKernel, collBatchKernel, llKernel under NCCL_AMD_WIDE_ACC): whether OP is
+// one, and the functor type such a kernel carries in OP's place (never called: the wide fold has no functor)
+constexpr bool isWideOp(int op) { return op == kOpWideSum || op == kOpWideAvg; }
+constexpr int redOpOf(int op) { return isWideOp(op) ? (int)DEV_SUM : op; }
+// The staged kernels' Avg scale: the f32 bits of the host's 1.0f / nRanks in the plan's redArg (enqueue.cc planColl)
+__device__ __forceinline__ float wideScaleOf(uint64_t redArg) { return u32AsF32((uint32_t)redArg); }
+
+// Packs per thread and batch of the STAGED wide fold (Channel::phaseB, oneShotB), the UMAX of foldRangeWide there.
+// The staged channel keeps more state live around the fold than symKernel (the slot and credit indexing, the push
+// list of the AG staging), so its budget is its own knob — but the zero-copy kernels' 4 / 2 packs fit: the widest
+// staged wide kernel, the batched 2-byte AllReduce, takes 121 of the 128 VGPRs, the fp8 ones at most 114, none with
+// scratch (DESIGN.md §2.8 has the table). 4 packs for fp8 would add 48 VGPRs (32 accumulators, 16 of loads).
+#ifndef NCCL_AMD_WIDE_STAGED_UNROLL_2B
+#define NCCL_AMD_WIDE_STAGED_UNROLL_2B 4
+#endif
+#ifndef NCCL_AMD_WIDE_STAGED_UNROLL_1B
+#define NCCL_AMD_WIDE_STAGED_UNROLL_1B 2
+#endif
+template <typename T>
+constexpr int kWideStagedUnroll = sizeof(T) > 1 ? NCCL_AMD_WIDE_STAGED_UNROLL_2B : NCCL_AMD_WIDE_STAGED_UNROLL_1B;
+
+template <typename T, bool AVG, int UMAX = 64>
 __device__ __forceinline__ void foldRangeWide(float scale, int n, const char* const* src, uint64_t nelem, char* dstLocal,
                                               char* const* dstPush, int nPush, bool aligned) {
   constexpr int EPP = Wide<T>::EPP;
-  constexpr int U = sizeof(T) > 1 ? kWideUnroll2B : kWideUnroll1B;
+  constexpr int U0 = sizeof(T) > 1 ? kWideUnroll2B : kWideUnroll1B;
+  constexpr int U = U0 < UMAX ? U0 : UMAX;
   // the sum (Avg: times 1/n, one f32 multiply) as the value the conversion rounds. fp16: kept opaque, or the
   // backend folds the multiply into v_fma_mixlo_f16(acc, scale, +0.0), which turns a -0 sum into +0 (opaqueF)
   auto result = [&](float acc) -> float {
@@ -840,7 +862,7 @@ struct Channel {
   const CollArgs& a;
   const DevComm& dc;
   Shared& sh;
-  const Red<T, OP>& fn;
+  const Red<T, redOpOf(OP)>& fn;
   int c, me, n, nSlots;
   bool aligned, isRoot, forceAcq, forceRel, noRel, noAcq;
   // AG pull (NCCL_AMD_AG_PULL=1, AllReduce / AllGather): phase B leaves ONE copy of the owner's block in
@@ -859,6 +881,11 @@ struct Channel {
   int cl;
   static constexpr uint64_t ts = sizeof(T);
   static constexpr bool kAR = COLL == COLL_AR || COLL == COLL_ARREF;
+  // NCCL_AMD_WIDE_ACC (OP = kOpWideSum / kOpWideAvg): phase B and one-shot B fold with foldRangeWide — f32
+  // accumulators, one rounding, the zero-copy kernels' contract bit for bit. All n contributions of an element lie at
+  // its owner there (its RS slots and its own sendbuff), so nothing else of the protocol changes: the credits, the
+  // slots, the mismatch probe, the pulls and the AG publication are the narrow kernel's.
+  static constexpr bool kWide = isWideOp(OP);
 
   __device__ uint64_t blockLen(int q) const {
     // Broadcast cuts its buffer with the host-callable functions of device_abi.h (blockLenOf / sliceBounds, the same
@@ -1047,7 +1074,10 @@ struct Channel {
       // (the reference-order kernel's extra indexing leaves the widest folds — 1-byte unpacked, 8-byte — fewer
       // packs in flight within the 128-VGPR co-residency budget)
       constexpr int kUMax = COLL != COLL_ARREF ? 64 : sizeof(T) == 1 ? 1 : sizeof(T) == 8 ? 2 : 64;
-      foldRange<T, OP, kUMax>(fn, n, sh.srcPtr, nelem, dstLocal, sh.pushPtr, sh.nPush, aligned);
+      if constexpr (kWide)
+        foldRangeWide<T, OP == kOpWideAvg, kWideStagedUnroll<T>>(wideScaleOf(a.redArg), n, sh.srcPtr, nelem, dstLocal,
+                                                                 sh.pushPtr, sh.nPush, aligned);
+      else foldRange<T, OP, kUMax>(fn, n, sh.srcPtr, nelem, dstLocal, sh.pushPtr, sh.nPush, aligned);
     }
     // one release covers both: AG data ready at each destination; RS slots consumed (ack to senders)
     if (tid < NCCL_AMD_MAX_RANKS) {
@@ -1125,7 +1155,10 @@ struct Channel {
       }
       __syncthreads();
       // sub-range starts inside a slot are 16-byte aligned: rank blocks are multiples of 16 bytes
-      foldRange<T, OP>(fn, n, sh.srcPtr, end - x, (char*)a.recvbuff + x * ts, sh.pushPtr, 0, aligned);
+      if constexpr (kWide)
+        foldRangeWide<T, OP == kOpWideAvg, kWideStagedUnroll<T>>(wideScaleOf(a.redArg), n, sh.srcPtr, end - x,
+                                                                 (char*)a.recvbuff + x * ts, sh.pushPtr, 0, aligned);
+      else foldRange<T, OP>(fn, n, sh.srcPtr, end - x, (char*)a.recvbuff + x * ts, sh.pushPtr, 0, aligned);
       __syncthreads();
       x = end;
     }
@@ -1328,7 +1361,7 @@ __device__ __forceinline__ uint64_t redArgOf(uint64_t arg, const void* ptr) {
 
 // One op's logical channel cl on physical channel c. False once a wait timed out (the comm aborts).
 template <typename T, int OP, int COLL>
-__device__ __forceinline__ bool runChannel(const CollArgs& a, const DevComm& dc, Shared& sh, const Red<T, OP>& fn,
+__device__ __forceinline__ bool runChannel(const CollArgs& a, const DevComm& dc, Shared& sh, const Red<T, redOpOf(OP)>& fn,
                                            int c, int cl) {
   // protoFlags: 1 = acquire on credit waits too, 2 = release on credit signals too, 4 = C(s) before A(s+1),
   // 8 = no release fence before data flags (the default: every published byte is a write-through system-scope
@@ -1382,7 +1415,7 @@ __global__ void __launch_bounds__(kThreads) kCoResident collKernel(CollArgs a) {
   const DevComm& dc = *a.comm;
   const int c = blockIdx.x;
   loadCounters(dc, sh, c);
-  const Red<T, OP> fn(redArgOf<T>(a.redArg, a.redArgPtr));
+  const Red<T, redOpOf(OP)> fn(redArgOf<T>(a.redArg, a.redArgPtr));
   runChannel<T, OP, COLL>(a, dc, sh, fn, c, c);
   storeCounters(dc, sh, c);
 }
@@ -1404,7 +1437,7 @@ __global__ void __launch_bounds__(kThreads) kCoResident collBatchKernel(CollBatc
     nchSh[threadIdx.x] = b.nch[threadIdx.x];
   }
   loadCounters(dc, sh, c);  // (ends with a workgroup barrier)
-  const Red<T, OP> fn(redArgOf<T>(b.op[0].redArg, b.op[0].redArgPtr));
+  const Red<T, redOpOf(OP)> fn(redArgOf<T>(b.op[0].redArg, b.op[0].redArgPtr));
   for (int k = 0; k < b.nOps; k++) {
     int j = c - chOffSh[k];
     if (j < 0) j += (int)gridDim.x;
@@ -1583,9 +1616,39 @@ __device__ __forceinline__ u32x4 loadLine16(const char* p) { return *(const vola
 // copy; not volatile, so the loads of several peers' lines can be in flight together.
 __device__ __forceinline__ u32x4 loadSeenLine16(const char* p) { return __builtin_nontemporal_load((const u32x4*)p); }
 
+// The wide fold of one 8-byte payload (NCCL_AMD_WIDE_ACC; pass 2 of llChannelOp / ll64ChannelOp under OP =
+// kOpWideSum / kOpWideAvg): 4 (2-byte types) or 8 (fp8) f32 accumulators, sources added in the fold order, one
+// multiply for Avg, one conversion. Per element with Wide<T>'s element forms — the instructions of foldRangeWide's
+// tails, whose results equal its pack forms' — so a payload stores the bits symKernel stores for the same inputs.
+template <typename T, bool AVG>
+struct WidePayload {
+  static constexpr int EPP = 8 / sizeof(T);
+  float acc[EPP];
+  __device__ __forceinline__ void add(uint64_t payload, bool first) {
+    union { uint64_t u; T e[EPP]; } x;
+    x.u = payload;
+#pragma unroll
+    for (int e = 0; e < EPP; e++) {
+      const float y = Wide<T>::toF(x.e[e]);
+      acc[e] = first ? y : y + acc[e];
+    }
+  }
+  __device__ __forceinline__ uint64_t result(float scale) const {
+    union { uint64_t u; T e[EPP]; } out;
+#pragma unroll
+    for (int e = 0; e < EPP; e++) {
+      float r = AVG ? acc[e] * scale : acc[e];
+      if (std::is_same<T, half_t>::value) r = opaqueF(r);  // (no v_fma_mixlo_f16 of the multiply: foldRangeWide)
+      out.e[e] = Wide<T>::fromF(r);
+    }
+    return out.u;
+  }
+};
+
+// (wideScale: the wide kernels' 1.0f / nRanks; unused by every other operator)
 template <typename T, int OP>
-__device__ __forceinline__ bool llChannelOp(const DevComm& dc, const Red<T, OP>& fn, const LLOp& op, int c, int j,
-                                            uint64_t e64, int& abortSh) {
+__device__ __forceinline__ bool llChannelOp(const DevComm& dc, const Red<T, redOpOf(OP)>& fn, const LLOp& op, int c, int j,
+                                            uint64_t e64, int& abortSh, float wideScale) {
   // c: physical channel (line area + epoch); j: this op's part index on it. Payload space: AllReduce the
   // whole buffer; ReduceScatter / AllGather one rank block (rank p's line for payload pk carries block p's
   // payload pk for ReduceScatter, its own input's payload pk for AllGather).
@@ -1706,6 +1769,15 @@ __device__ __forceinline__ bool llChannelOp(const DevComm& dc, const Red<T, OP>&
     const int owner = op.coll == LL_RS ? me
                     : op.coll == LL_REDUCE ? op.root
                     : (int)((pk * 8 / sizeof(T)) / op.chunk);  // an AllReduce payload never straddles blocks
+    if constexpr (isWideOp(OP)) {
+      WidePayload<T, OP == kOpWideAvg> w;
+      for (int k = 0; k < n; k++) {
+        const int q = (owner + 1 + k) % n;
+        w.add(q == me ? myV : llPayload(loadSeenLine16(myLL + llLineOffset(dc, c, par, q) + (pk - lo) * 16)), k == 0);
+      }
+      storePayload(recv, pk, w.result(wideScale));
+      continue;
+    }
     union { uint64_t u; T e[EPP]; } acc, x;
     for (int k = 0; k < n; k++) {
       int q = (owner + 1 + k) % n;
@@ -1738,8 +1810,8 @@ __device__ __forceinline__ bool llChannelOp(const DevComm& dc, const Red<T, OP>&
 // the line area is its own (ll64LineOffset), so neither protocol can mistake the other's payload for a flag.
 
 template <typename T, int OP>
-__device__ __forceinline__ bool ll64ChannelOp(const DevComm& dc, const Red<T, OP>& fn, const LLOp& op, int c, int j,
-                                              uint64_t e64, int& abortSh) {
+__device__ __forceinline__ bool ll64ChannelOp(const DevComm& dc, const Red<T, redOpOf(OP)>& fn, const LLOp& op, int c, int j,
+                                              uint64_t e64, int& abortSh, float wideScale) {
   const int tid = threadIdx.x, lane = tid & 63, me = dc.rank, n = dc.nRanks;
   constexpr int EPP = 8 / sizeof(T);
   const uint32_t flag = (uint32_t)e64 ? (uint32_t)e64 : 1u;
@@ -1889,6 +1961,30 @@ __device__ __forceinline__ bool ll64ChannelOp(const DevComm& dc, const Red<T, OP
       }
       return loadSeenLine16(myLL + ll64LineOffset(dc, c, par, q) + off);
     };
+    if constexpr (isWideOp(OP)) {
+      // the wide fold: one f32 accumulator set per payload of the unit. Where both share the owner (everywhere but
+      // at a block boundary) one walk of the sources feeds both; at a boundary each payload walks its own order
+      WidePayload<T, OP == kOpWideAvg> w0, w1;
+      const bool both = two && own0 == own1;
+      u32x4 nxt = fetch(own0, 0);
+      for (int k = 0; k < n; k++) {
+        const u32x4 cur = nxt;
+        if (k + 1 < n) nxt = fetch(own0, k + 1);
+        w0.add(cur.x | ((uint64_t)cur.y << 32), k == 0);
+        if (both) w1.add(cur.z | ((uint64_t)cur.w << 32), k == 0);
+      }
+      storePayload(recv, pk, w0.result(wideScale));
+      if (two && !both) {
+        nxt = fetch(own1, 0);
+        for (int k = 0; k < n; k++) {
+          const u32x4 cur = nxt;
+          if (k + 1 < n) nxt = fetch(own1, k + 1);
+          w1.add(cur.z | ((uint64_t)cur.w << 32), k == 0);
+        }
+      }
+      if (two) storePayload(recv, pk + 1, w1.result(wideScale));
+      continue;
+    }
     // fold payload h (0: low 8 bytes of the unit, 1: high 8 bytes) in owner's order
     auto foldOne = [&](int owner, int h) {
       union { uint64_t u; T e[EPP]; } acc, x;
@@ -2361,7 +2457,8 @@ __global__ void __launch_bounds__(kThreads) kCoResident llKernel(LLArgs<K> a) {
     opArg = 0;
     __builtin_memcpy(&opArg, a.redArgPtr, sizeof(T));
   }
-  const Red<T, OP> fn(opArg);
+  const Red<T, redOpOf(OP)> fn(opArg);
+  const float wideScale = wideScaleOf(a.redArg);  // (the wide kernels alone read it: NCCL_AMD_WIDE_ACC, WidePayload)
   uint64_t e64 = a.counters[ctrIndex(c, CTR_LL, 0)];
   __syncthreads();
   const int L = dc.llChannels;
@@ -2387,8 +2484,8 @@ __global__ void __launch_bounds__(kThreads) kCoResident llKernel(LLArgs<K> a) {
         continue;
       }
     }
-    const bool ok = P == LLP_LL64 ? ll64ChannelOp<T, OP>(dc, fn, o, c, j, e64, abortSh)
-                                  : llChannelOp<T, OP>(dc, fn, o, c, j, e64, abortSh);
+    const bool ok = P == LLP_LL64 ? ll64ChannelOp<T, OP>(dc, fn, o, c, j, e64, abortSh, wideScale)
+                                  : llChannelOp<T, OP>(dc, fn, o, c, j, e64, abortSh, wideScale);
     if (!ok) break;
   }
   if (threadIdx.x == 0) a.counters[ctrIndex(c, CTR_LL, 0)] = e64;
@@ -3018,6 +3115,34 @@ inline ncclResult_t launchOp(const LaunchPlan& p) {
   }
   WARN("internal: op %d unsupported for this type", p.devOp);
   return ncclInternalError;
+}
+// fp16 / bf16 / fp8 (their units alone instantiate the staged and LL wide kernels): a plan marked wide
+// (NCCL_AMD_WIDE_ACC, enqueue.cc planColl) runs them — single ops and group batches, as launchSymSmallFloat does for
+// the zero-copy plans. Only the plans that fold at one owner are ever marked.
+template <typename T, int OP>
+inline ncclResult_t launchWideTyped(const LaunchPlan& p) {
+  const bool staged = p.algo == ALGO_DIRECT || p.algo == ALGO_ONESHOT;
+  if (p.algo == ALGO_LL && (p.func == FUNC_ALLREDUCE || p.func == FUNC_REDUCESCATTER || p.func == FUNC_REDUCE)) {
+    launchLL<T, OP>(p);
+  } else if (staged && !p.args.cbdLo && p.func == FUNC_ALLREDUCE) {
+    if (p.algo == ALGO_ONESHOT) launchColl<T, OP, COLL_AR1>(p);
+    else launchColl<T, OP, COLL_AR>(p);
+  } else if (p.algo == ALGO_DIRECT && p.func == FUNC_REDUCESCATTER) {
+    launchColl<T, OP, COLL_RS>(p);
+  } else if (p.algo == ALGO_DIRECT && p.func == FUNC_REDUCE) {
+    launchColl<T, OP, COLL_REDUCE>(p);
+  } else {
+    WARN("internal: no wide kernel for function %d on algorithm %d", (int)p.func, p.algo);
+    return ncclInternalError;
+  }
+  HIPCHECK(hipGetLastError());
+  return ncclSuccess;
+}
+template <typename T>
+inline ncclResult_t launchSmallFloatOp(const LaunchPlan& p) {
+  if (p.wide == 1) return launchWideTyped<T, kOpWideSum>(p);
+  if (p.wide == 2) return launchWideTyped<T, kOpWideAvg>(p);
+  return launchOp<T>(p);
 }
 template <typename T>
 inline ncclResult_t launchIntOp(const LaunchPlan& p) {

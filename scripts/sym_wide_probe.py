@@ -2,14 +2,18 @@
 """One-GPU probe of the wide-accumulator fold of the zero-copy AllReduce (NCCL_AMD_SYM_WIDE_ACC=1, kernels.h
 foldRangeWide) beside the default per-hop fold of the same data.
 
-  sym_wide_probe.py [--warmup 5] [--iters 10] [--rounds 3] [--step-timeout 300] [--out FILE.json]
+  sym_wide_probe.py [--mode sym|staged] [--warmup 5] [--iters 10] [--rounds 3] [--step-timeout 300] [--out FILE.json]
 
 Two communicators of 4 ranks each in one process on GPU 0 (NCCL_MULTI_RANK_GPU_ENABLE=1), one created with the knob and
 one without (it is read at communicator init). bf16 and e4m3 AllReduce Sum of 64 MiB per rank, out of place, on
 symmetric windows; the two communicators alternate inside every round; a call's time is the slowest rank's HIP event
 pair around it. The measurement runs in a child process started with a time limit. Both folds read the same bytes and
 write the same bytes; they differ in the ALU work per element. No byte crosses an xGMI link here: the figures are
-HBM-bound rehearsal records and say nothing about link speed. No default and no threshold is derived from them."""
+HBM-bound rehearsal records and say nothing about link speed. No default and no threshold is derived from them.
+
+--mode staged: the same method on the staged direct AllReduce (NCCL_AMD_WIDE_ACC=1 beside the per-hop fold): plain
+buffers in no window, NCCL_PROTO=^LL, the size far above the one-shot range, so collKernel's phase B folds. The scatter
+and the gather around the fold are the same copies in both communicators."""
 import argparse
 import json
 import os
@@ -34,11 +38,16 @@ def run_step(a):
     torch.cuda.set_device(0)
     n, nbytes = N_RANKS, NBYTES
     comms, wins, handles, streams = {}, {}, {}, {}
+    staged = a.mode == "staged"
+    if staged:
+        os.environ["NCCL_PROTO"] = "^LL"
     for kind in KINDS:
-        os.environ["NCCL_AMD_SYM_WIDE_ACC"] = "1" if kind == "wide" else "0"
+        os.environ["NCCL_AMD_WIDE_ACC" if staged else "NCCL_AMD_SYM_WIDE_ACC"] = "1" if kind == "wide" else "0"
         comms[kind] = nccl_amd.Communicator.init_all([0] * n)
         streams[kind] = [torch.cuda.Stream() for _ in range(n)]
         wins[kind] = [torch.zeros(2 * nbytes, dtype=torch.uint8, device="cuda") for _ in range(n)]  # [send | recv]
+        if staged:  # plain buffers: no window, no registration
+            continue
         with nccl_amd.group():
             handles[kind] = [c.register_window(w.data_ptr(), 2 * nbytes) for c, w in zip(comms[kind], wins[kind])]
 
@@ -90,12 +99,14 @@ def run_step(a):
                      "result_bytes_that_differ_rank0": differ}
     errs = [c.async_error() for k in KINDS for c in comms[k]]
     for kind in KINDS:
-        for c, h in zip(comms[kind], handles[kind]):
+        for c, h in zip(comms[kind], handles.get(kind, [])):
             c.deregister_window(h)
         for c in comms[kind]:
             c.destroy()
-    res = {"what": "zero-copy AllReduce Sum on symmetric windows with the wide-accumulator fold (NCCL_AMD_SYM_WIDE_ACC=1) "
-                   "beside the per-hop fold, two communicators of one process on one GPU (no xGMI link is crossed)",
+    what = ("staged direct AllReduce Sum on plain buffers (NCCL_PROTO=^LL) with the wide-accumulator fold (NCCL_AMD_WIDE_ACC=1) "
+            if staged else
+            "zero-copy AllReduce Sum on symmetric windows with the wide-accumulator fold (NCCL_AMD_SYM_WIDE_ACC=1) ")
+    res = {"what": what + "beside the per-hop fold, two communicators of one process on one GPU (no xGMI link is crossed)",
            "n_ranks": n, "bytes_per_rank": nbytes, "warmup": a.warmup, "iters_per_round": a.iters,
            "timing": "HIP events on every rank's stream around the call, slowest rank; the two communicators alternate",
            "types": out, "async_errors": errs, "device": torch.cuda.get_device_name(0)}
@@ -105,6 +116,7 @@ def run_step(a):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=("sym", "staged"), default="sym")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
@@ -114,7 +126,7 @@ def main():
     a = ap.parse_args()
     if a.child:
         return run_step(a)
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--warmup", str(a.warmup), "--iters", str(a.iters),
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--mode", a.mode, "--warmup", str(a.warmup), "--iters", str(a.iters),
            "--rounds", str(a.rounds)]
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=a.step_timeout)
