@@ -292,6 +292,7 @@ struct CommTuning {
   int symWtPublish;         // NCCL_AMD_SYM_WT: symmetric kernels publish with write-through stores, no L2 write-back
   int symWideAcc;           // NCCL_AMD_SYM_WIDE_ACC: zero-copy fp16 / bf16 / fp8 Sum and Avg accumulate in f32, one rounding
   int wideAcc;              // NCCL_AMD_WIDE_ACC: that (it sets symWideAcc) and the same fold on the direct, one-shot and LL plans
+  int wireBf16;             // NCCL_AMD_WIRE_BF16: fp32 Sum / Avg AllReduce and ReduceScatter on the direct plan stage and send bf16
   int localRegister;       // NCCL_LOCAL_REGISTER: ncclCommRegister maps buffers into peers (zero-copy collectives)
   int graphRegister;        // NCCL_GRAPH_REGISTER: buffers of captured collectives are registered automatically
   int noAggregation;        // NCCL_AMD_NO_AGGREGATION
@@ -523,6 +524,13 @@ struct LaunchPlan {  // one kernel launch (reference: struct ncclKernelPlan, src
   // 16- / 8-bit float fold in f32 with one rounding (kernels.h foldRangeWide); args.redArg / ll.redArg then hold
   // the f32 bits of 1.0f / nRanks. Part of the batch key (enqueue.cc sameRedOp)
   int wide;
+  // NCCL_AMD_WIRE_BF16 on a single fp32 Sum (1) / Avg (2) AllReduce or ReduceScatter of ALGO_DIRECT: the staging slots
+  // and the links carry bf16 (kernels.h Channel::kWire). args then holds the cut for the 2-byte wire
+  // element and redArg the f32 bits of 1.0f / nRanks; the full-width plan stays in narrow*, which a group batch puts
+  // back (enqueue.cc launchBatch: collBatchKernel has no wire variant). Part of the batch key (sameRedOp)
+  int wire;
+  CollArgs narrowArgs;
+  int narrowDevOp, narrowChannels;
 };
 
 ncclResult_t enqueueCheck(CollInfo* info);

@@ -246,6 +246,10 @@ void loadTuning(CommTuning* t) {
   // §2.8). NCCL_AMD_SYM_WIDE_ACC alone leaves the staged plans per-hop
   t->wideAcc = (int)paramInt("NCCL_AMD_WIDE_ACC", 0) != 0;
   if (t->wideAcc) t->symWideAcc = 1;
+  // NCCL_AMD_WIRE_BF16=1: an fp32 Sum / Avg AllReduce or ReduceScatter on the staged direct plan rounds every
+  // contribution to bf16 once, stages and sends bf16 and folds in f32 (kernels.h Channel::kWire):
+  // half the link bytes, fp32 user buffers at both ends. 0 (default): the full-width wire
+  t->wireBf16 = (int)paramInt("NCCL_AMD_WIRE_BF16", 0) != 0;
   // reference register.cc:16 / enqueue.cc:283 (both default on): ncclCommRegister'd buffers and, under stream
   // capture, the captured collectives' buffers run the zero-copy kernel (register.cc)
   t->localRegister = (int)paramInt("NCCL_LOCAL_REGISTER", 1);
@@ -1171,11 +1175,35 @@ ncclResult_t planColl(const CollInfo& info, LaunchPlan& p, SymPlan& sp, int* kin
     int maxCh = comm->chanCap;
     if (n >= 3 && comm->tune.linkChannels > 0 && tunedNch == 0) maxCh = std::min(maxCh, comm->tune.linkChannels);
     planChannels(comm, blockElems * ts, ts, p, minPart, maxCh);
+    // NCCL_AMD_WIRE_BF16: the built-in Sum and Avg of an fp32 AllReduce / ReduceScatter that reached this plan stage
+    // and send bf16. From the agreed knob, the function, the datatype, the op and the chosen plan
+    // alone — never a pointer or a role — so every rank runs the same kernel. The cut is made again for the 2-byte
+    // wire element: rank blocks, channel parts and slices in whole wire packs of 8 elements, a slot holding slotBytes / 2
+    // elements, channels by the wire bytes. The operator becomes the wire one: no functor argument, the Avg scale as
+    // the f32 bits of 1.0f / n. The full-width plan is kept for a group batch (launchBatch)
+    const int wire = !comm->tune.wireBf16 || info.datatype != ncclFloat32 ||
+                             (info.func != FUNC_ALLREDUCE && info.func != FUNC_REDUCESCATTER) ? 0
+                     : info.op == ncclSum ? 1 : info.op == ncclAvg ? 2 : 0;
+    if (wire) {
+      constexpr uint64_t kWireElt = 2, kWirePack = 16 / kWireElt;
+      p.narrowArgs = p.args;
+      p.narrowDevOp = p.devOp;
+      p.narrowChannels = p.nChannels;
+      if (info.func == FUNC_ALLREDUCE) p.args.chunk = blockElems = ((count + n - 1) / n + kWirePack - 1) / kWirePack * kWirePack;
+      minPart = tunedNch > 0 ? (blockElems * kWireElt + tunedNch - 1) / tunedNch : (size_t)comm->tune.minChannelBytes;
+      planChannels(comm, blockElems * kWireElt, (int)kWireElt, p, minPart, maxCh);
+      const float r = 1.0f / (float)n;
+      p.wire = wire;
+      p.devOp = DEV_SUM;
+      p.args.redArg = 0;
+      memcpy(&p.args.redArg, &r, sizeof(r));
+      p.args.redArgPtr = nullptr;
+    }
   }
   if (wide) markWide();
-  TRACE("%s: count %zu dt %d op %d -> nch %d part %lu slice %lu steps %d aligned %d%s", info.opName, count,
+  TRACE("%s: count %zu dt %d op %d -> nch %d part %lu slice %lu steps %d aligned %d%s%s", info.opName, count,
         (int)info.datatype, (int)info.op, p.nChannels, (unsigned long)p.args.part, (unsigned long)p.args.slice,
-        p.args.nSteps, p.args.aligned, wide ? " wide 1" : "");
+        p.args.nSteps, p.args.aligned, wide ? " wide 1" : "", p.wire ? " wire bf16" : "");
   return ncclSuccess;
 }
 
@@ -1257,7 +1285,7 @@ void collProgress(ncclComm* comm, hipStream_t stream) {
 // (collBatchKernel). Every rank of a comm issues the same op sequence and plans each op alike, so every
 // rank forms the same batches.
 static bool sameRedOp(const LaunchPlan& a, const LaunchPlan& b) {
-  return a.devOp == b.devOp && a.wide == b.wide && a.args.redArg == b.args.redArg && a.args.redArgPtr == b.args.redArgPtr;
+  return a.devOp == b.devOp && a.wide == b.wide && a.wire == b.wire && a.args.redArg == b.args.redArg && a.args.redArgPtr == b.args.redArgPtr;
 }
 
 bool batchable(const std::vector<PlannedColl>& run, const PlannedColl& b) {
@@ -1334,6 +1362,15 @@ ncclResult_t launchBatch(std::vector<PlannedColl>& run) {
     noteLaunch(comm, p.stream);
     return ncclSuccess;
   }
+  // (a batch keeps the full-width wire: ops planned for the bf16 wire take their narrow plan back — all of them or
+  // none, the wire mark being part of the batch key)
+  for (PlannedColl& x : run)
+    if (x.p.wire) {
+      x.p.args = x.p.narrowArgs;
+      x.p.devOp = x.p.narrowDevOp;
+      x.p.nChannels = x.p.narrowChannels;
+      x.p.wire = 0;
+    }
   CollBatchArgs& b = p.batch;
   int off = 0, used = 0;
   for (size_t k = 0; k < run.size(); k++) {

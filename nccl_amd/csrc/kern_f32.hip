@@ -2,7 +2,7 @@
 #include "kernels.h"
 namespace ncclamd {
 ncclResult_t launchKernF32(const LaunchPlan& p) {
-  return launchOp<float>(p);
+  return launchF32Op(p);  // launchOp<float>, or the bf16-wire kernels (NCCL_AMD_WIRE_BF16)
 }
 // Force this code object to load now (see warmKernels in kernels.hip).
 hipError_t warmKernF32() {

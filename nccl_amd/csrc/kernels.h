@@ -726,7 +726,11 @@ struct Wide {
 // The wide operators outside symKernel (collKernel, collBatchKernel, llKernel under NCCL_AMD_WIDE_ACC): whether OP is
 // one, and the functor type such a kernel carries in OP's place (never called: the wide fold has no functor)
 constexpr bool isWideOp(int op) { return op == kOpWideSum || op == kOpWideAvg; }
-constexpr int redOpOf(int op) { return isWideOp(op) ? (int)DEV_SUM : op; }
+// ... and the bf16-wire operators of the fp32 direct kernels (NCCL_AMD_WIRE_BF16, below): collKernel<float, kOpWireSum /
+// kOpWireAvg, COLL_AR / COLL_RS>, no functor either
+constexpr int kOpWireSum = 18, kOpWireAvg = 19;
+constexpr bool isWireOp(int op) { return op == kOpWireSum || op == kOpWireAvg; }
+constexpr int redOpOf(int op) { return isWideOp(op) || isWireOp(op) ? (int)DEV_SUM : op; }
 // The staged kernels' Avg scale: the f32 bits of the host's 1.0f / nRanks in the plan's redArg (enqueue.cc planColl)
 __device__ __forceinline__ float wideScaleOf(uint64_t redArg) { return u32AsF32((uint32_t)redArg); }
 
@@ -817,6 +821,203 @@ __device__ __forceinline__ void foldRangeWide(float scale, int n, const char* co
   if (t < nelem) element(t);
 }
 
+// ------------------------------------------------------------------------------------ bf16 wire of the fp32 direct plan
+//
+// NCCL_AMD_WIRE_BF16: an fp32 Sum / Avg AllReduce or ReduceScatter on the staged direct plan whose
+// staging slots and links carry bf16 — half the link bytes — between fp32 user buffers. Every contribution, the
+// owner's own included, is rounded to bf16 once (v_cvt_pk_bf16_f32, Wide<bf16_t>::pack / Traits<bf16_t>::fromF); the n
+// rounded values are added in f32 in the fold order; Avg multiplies once by the host's 1.0f / n; ReduceScatter stores
+// that f32 value, AllReduce rounds it once to bf16 and every rank, the owner too, stores the bf16 value widened. The
+// conversions ride in the copies the direct channel makes anyway: phase A reads two fp32 packs and stores one wire
+// pack (wireScatter), phase B folds n-1 wire sources and the rounded own fp32 slice (wireFold), phase C reads one
+// wire pack and stores two fp32 packs (wireGather). A wire pack is 16 bytes = 8 elements = two fp32 packs, so the
+// plan is cut in multiples of 8 elements (enqueue.cc planColl); ranges are counted in elements here. Tails and
+// unaligned ranges go per element with the same conversions, so both paths store the same bits.
+typedef Wide<bf16_t> Wire;
+constexpr int kWirePack = Wire::EPP;  // elements of a wire pack
+// Wire packs per thread and batch: wireScatter keeps 2 x kWireCopyUnroll fp32 packs in flight (copyRange's 8), wireGather
+// kWireCopyUnroll wire packs (and twice the stores); wireFold holds per pack 8 accumulators, the current and the next
+// wire source (8) and the own slice's two fp32 packs (8). Register figures of both choices: DESIGN.md §2.10.
+#ifndef NCCL_AMD_WIRE_COPY_UNROLL
+#define NCCL_AMD_WIRE_COPY_UNROLL 4
+#endif
+#ifndef NCCL_AMD_WIRE_FOLD_UNROLL
+#define NCCL_AMD_WIRE_FOLD_UNROLL 2
+#endif
+constexpr int kWireCopyUnroll = NCCL_AMD_WIRE_COPY_UNROLL;
+constexpr int kWireFoldUnroll = NCCL_AMD_WIRE_FOLD_UNROLL;
+
+// two fp32 packs -> one wire pack (one rounding per element); one wire pack -> two fp32 packs (exact)
+__device__ __forceinline__ u32x4 wireNarrow(u32x4 lo, u32x4 hi) {
+  float f[kWirePack];
+#pragma unroll
+  for (int e = 0; e < 4; e++) f[e] = u32AsF32(lo[e]), f[4 + e] = u32AsF32(hi[e]);
+  return Wire::pack(f);
+}
+__device__ __forceinline__ void wireWiden(u32x4 w, u32x4& lo, u32x4& hi) {
+  float f[kWirePack];
+  Wire::unpack(w, f);
+#pragma unroll
+  for (int e = 0; e < 4; e++) lo[e] = f32AsU32(f[e]), hi[e] = f32AsU32(f[4 + e]);
+}
+
+// Phase A: fp32 src[0, nelem) -> bf16 dst (a staging slot: remote stores, the peer's slab or, under the RS pull, mine)
+__device__ __forceinline__ void wireScatter(char* dst, const float* src, uint64_t nelem, bool aligned) {
+  bf16_t* de = (bf16_t*)dst;
+  if (!aligned) {
+    for (uint64_t t = threadIdx.x; t < nelem; t += kThreads) storeRemoteElt(de + t, Wire::fromF(src[t]));
+    return;
+  }
+  const uint64_t npk = nelem / kWirePack;
+  const u32x4* s = (const u32x4*)src;
+  u32x4* d = (u32x4*)dst;
+  constexpr int U = kWireCopyUnroll;
+  uint64_t i = threadIdx.x;
+  for (; i + (U - 1) * kThreads < npk; i += U * kThreads) {
+    u32x4 lo[U], hi[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      lo[u] = __builtin_nontemporal_load(s + 2 * (i + u * kThreads));
+      hi[u] = __builtin_nontemporal_load(s + 2 * (i + u * kThreads) + 1);
+    }
+    const __amdgpu_buffer_rsrc_t rd = remoteRsrc(d + (i - threadIdx.x));  // (rebased per batch, as in copyRange)
+#pragma unroll
+    for (int u = 0; u < U; u++) storeRemoteAt(rd, (uint32_t)((threadIdx.x + u * kThreads) * 16), wireNarrow(lo[u], hi[u]));
+  }
+  for (; i < npk; i += kThreads) {
+    const u32x4 lo = __builtin_nontemporal_load(s + 2 * i), hi = __builtin_nontemporal_load(s + 2 * i + 1);
+    storeRemoteAt(remoteRsrc(d + (i - threadIdx.x)), threadIdx.x * 16u, wireNarrow(lo, hi));
+  }
+  const uint64_t t = npk * kWirePack + threadIdx.x;  // < one wire pack of tail
+  if (t < nelem) storeRemoteElt(de + t, Wire::fromF(src[t]));
+}
+
+// Phase C: bf16 src[0, nelem) (an AG slot, mine or under the pull the owner's) -> fp32 dst (my recvbuff)
+__device__ __forceinline__ void wireGather(float* dst, const char* src, uint64_t nelem, bool aligned) {
+  const bf16_t* se = (const bf16_t*)src;
+  if (!aligned) {
+    for (uint64_t t = threadIdx.x; t < nelem; t += kThreads) dst[t] = Wire::toF(se[t]);
+    return;
+  }
+  const uint64_t npk = nelem / kWirePack;
+  const u32x4* s = (const u32x4*)src;
+  constexpr int U = kWireCopyUnroll;
+  uint64_t i = threadIdx.x;
+  for (; i + (U - 1) * kThreads < npk; i += U * kThreads) {
+    u32x4 v[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) v[u] = __builtin_nontemporal_load(s + i + u * kThreads);
+    LocalStore ls(dst, 2 * (i - threadIdx.x));
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      u32x4 lo, hi;
+      wireWiden(v[u], lo, hi);
+      ls.put(2 * (threadIdx.x + u * kThreads), lo);
+      ls.put(2 * (threadIdx.x + u * kThreads) + 1, hi);
+    }
+  }
+  for (; i < npk; i += kThreads) {
+    u32x4 lo, hi;
+    wireWiden(__builtin_nontemporal_load(s + i), lo, hi);
+    __builtin_nontemporal_store(lo, (u32x4*)dst + 2 * i);
+    __builtin_nontemporal_store(hi, (u32x4*)dst + 2 * i + 1);
+  }
+  const uint64_t t = npk * kWirePack + threadIdx.x;
+  if (t < nelem) dst[t] = Wire::toF(se[t]);
+}
+
+// Phase B: src[0 .. n-2] are the peers' bf16 slices in fold order (staging), src[n-1] the owner's own fp32 slice — the
+// owner closes its block's fold order (owner+1, ..., owner). f32 accumulators, shaped like foldRangeWide: the next
+// source's packs load while the current one folds (the own slice's two fp32 packs behind the last wire source, the
+// next batch's first source behind the own slice). AR: the result rounded once to bf16, one wire pack to each of the
+// nPush AG destinations and, widened, two fp32 packs to dstLocal; RS (!AR): two fp32 packs of the f32 result.
+template <bool AVG, bool AR>
+__device__ __forceinline__ void wireFold(float scale, int n, const char* const* src, uint64_t nelem, float* dstLocal,
+                                         char* const* dstPush, int nPush, bool aligned) {
+  constexpr int U = kWireFoldUnroll;
+  auto element = [&](uint64_t t) {
+    float acc = Wire::toF(((const bf16_t*)src[0])[t]);
+    for (int k = 1; k + 1 < n; k++) acc = Wire::toF(((const bf16_t*)src[k])[t]) + acc;
+    acc = Wire::toF(Wire::fromF(((const float*)src[n - 1])[t])) + acc;
+    if (AVG) acc = acc * scale;
+    if (AR) {
+      const bf16_t out = Wire::fromF(acc);
+      for (int p = 0; p < nPush; p++) storeRemoteElt((bf16_t*)dstPush[p] + t, out);
+      acc = Wire::toF(out);
+    }
+    dstLocal[t] = acc;
+  };
+  if (!aligned) {
+    for (uint64_t t = threadIdx.x; t < nelem; t += kThreads) element(t);
+    return;
+  }
+  const uint64_t npk = nelem / kWirePack;
+  const uint64_t step = (uint64_t)U * kThreads;
+  const u32x4* own = (const u32x4*)src[n - 1];
+  float acc[U][kWirePack];
+  u32x4 cur[U], nxt[U], ownLo[U], ownHi[U];
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+    const uint64_t i = threadIdx.x + (uint64_t)u * kThreads;
+    if (i < npk) cur[u] = __builtin_nontemporal_load((const u32x4*)src[0] + i);
+  }
+  for (uint64_t base = threadIdx.x; base < npk; base += step) {
+    for (int k = 0; k < n; k++) {
+      const bool isOwn = k + 1 == n;
+      if (k + 2 == n) {  // behind the last wire source: the own slice's fp32 packs
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          const uint64_t i = base + (uint64_t)u * kThreads;
+          if (i < npk) ownLo[u] = __builtin_nontemporal_load(own + 2 * i), ownHi[u] = __builtin_nontemporal_load(own + 2 * i + 1);
+        }
+      } else if (!isOwn || base + step < npk) {  // the next wire source; behind the own slice, the next batch's first
+        const u32x4* s = (const u32x4*)src[isOwn ? 0 : k + 1];
+        const uint64_t b = isOwn ? base + step : base;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          const uint64_t i = b + (uint64_t)u * kThreads;
+          if (i < npk) nxt[u] = __builtin_nontemporal_load(s + i);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        float x[kWirePack];
+        Wire::unpack(isOwn ? wireNarrow(ownLo[u], ownHi[u]) : cur[u], x);
+#pragma unroll
+        for (int e = 0; e < kWirePack; e++) acc[u][e] = k == 0 ? x[e] : x[e] + acc[u][e];
+        if (k + 2 != n) cur[u] = nxt[u];
+      }
+    }
+    LocalStore ls(dstLocal, 2 * (base - threadIdx.x));
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const uint64_t i = base + (uint64_t)u * kThreads;
+      if (i >= npk) continue;
+      if (AVG) {
+#pragma unroll
+        for (int e = 0; e < kWirePack; e++) acc[u][e] = acc[u][e] * scale;
+      }
+      u32x4 lo, hi;
+      if (AR) {
+        const u32x4 out = Wire::pack(acc[u]);
+        for (int p = 0; p < nPush; p++) {  // (resource rebased on the batch's first pack, as in foldRange)
+          if (NCCL_AMD_BUFFER_STORES)
+            storeRemoteAt(remoteRsrc((u32x4*)dstPush[p] + (base - threadIdx.x)), (threadIdx.x + u * kThreads) * 16u, out);
+          else storeRemote((u32x4*)dstPush[p] + i, out);
+        }
+        wireWiden(out, lo, hi);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; e++) lo[e] = f32AsU32(acc[u][e]), hi[e] = f32AsU32(acc[u][4 + e]);
+      }
+      ls.put(2 * (threadIdx.x + u * kThreads), lo);
+      ls.put(2 * (threadIdx.x + u * kThreads) + 1, hi);
+    }
+  }
+  const uint64_t t = npk * kWirePack + threadIdx.x;  // < one wire pack of tail
+  if (t < nelem) element(t);
+}
+
 
 // ------------------------------------------------------------------------------------ collective kernel
 
@@ -886,6 +1087,14 @@ struct Channel {
   // its owner there (its RS slots and its own sendbuff), so nothing else of the protocol changes: the credits, the
   // slots, the mismatch probe, the pulls and the AG publication are the narrow kernel's.
   static constexpr bool kWide = isWideOp(OP);
+  // NCCL_AMD_WIRE_BF16 (OP = kOpWireSum / kOpWireAvg; T = float, AllReduce / ReduceScatter): the staging slots hold
+  // bf16 — phase A narrows (wireScatter), phase B folds bf16 sources and the rounded own slice in f32 (wireFold), phase
+  // C widens (wireGather). The plan is cut for the 2-byte wire element (a.chunk, a.part, a.slice in whole wire packs,
+  // a slice of at most slotBytes / 2 elements); the credits, the slots, the counters, the flags, peerAt, the pulls, the
+  // spins and the mismatch probe are the narrow kernel's.
+  static constexpr bool kWire = isWireOp(OP);
+  static_assert(!kWire || (std::is_same<T, float>::value && (COLL == COLL_AR || COLL == COLL_RS)),
+                "the bf16 wire: fp32 AllReduce and ReduceScatter on the direct plan");
 
   __device__ uint64_t blockLen(int q) const {
     // Broadcast cuts its buffer with the host-callable functions of device_abi.h (blockLenOf / sliceBounds, the same
@@ -1001,7 +1210,8 @@ struct Channel {
       char* dst = rsPull ? dc.staging[me] + stagingOffset(dc, c, STG_RS, slot, p)   // my slab, area for p
                          : dc.staging[p] + stagingOffset(dc, c, STG_RS, slot, me);
       const char* src = (const char*)a.sendbuff + off * ts;
-      copyRange<T, true>(dst, src, len * ts, aligned);
+      if constexpr (kWire) wireScatter(dst, (const float*)src, len, aligned);
+      else copyRange<T, true>(dst, src, len * ts, aligned);
     }
     if (tid < NCCL_AMD_MAX_RANKS) {
       bool act = tid < n && tid != me && owns(tid);
@@ -1074,7 +1284,10 @@ struct Channel {
       // (the reference-order kernel's extra indexing leaves the widest folds — 1-byte unpacked, 8-byte — fewer
       // packs in flight within the 128-VGPR co-residency budget)
       constexpr int kUMax = COLL != COLL_ARREF ? 64 : sizeof(T) == 1 ? 1 : sizeof(T) == 8 ? 2 : 64;
-      if constexpr (kWide)
+      if constexpr (kWire)  // (srcPtr[n - 1] is my own fp32 slice: the owner closes the fold order)
+        wireFold<OP == kOpWireAvg, kAR>(wideScaleOf(a.redArg), n, sh.srcPtr, nelem, (float*)dstLocal, sh.pushPtr, sh.nPush,
+                                        aligned);
+      else if constexpr (kWide)
         foldRangeWide<T, OP == kOpWideAvg, kWideStagedUnroll<T>>(wideScaleOf(a.redArg), n, sh.srcPtr, nelem, dstLocal,
                                                                  sh.pushPtr, sh.nPush, aligned);
       else foldRange<T, OP, kUMax>(fn, n, sh.srcPtr, nelem, dstLocal, sh.pushPtr, sh.nPush, aligned);
@@ -1158,7 +1371,7 @@ struct Channel {
       if constexpr (kWide)
         foldRangeWide<T, OP == kOpWideAvg, kWideStagedUnroll<T>>(wideScaleOf(a.redArg), n, sh.srcPtr, end - x,
                                                                  (char*)a.recvbuff + x * ts, sh.pushPtr, 0, aligned);
-      else foldRange<T, OP>(fn, n, sh.srcPtr, end - x, (char*)a.recvbuff + x * ts, sh.pushPtr, 0, aligned);
+      else foldRange<T, redOpOf(OP)>(fn, n, sh.srcPtr, end - x, (char*)a.recvbuff + x * ts, sh.pushPtr, 0, aligned);
       __syncthreads();
       x = end;
     }
@@ -1192,7 +1405,8 @@ struct Channel {
       const char* src = agPull ? dc.staging[q] + stagingOffset(dc, c, STG_AG, slot, q)  // q's own copy, remote
                                : dc.staging[me] + stagingOffset(dc, c, STG_AG, slot, q);
       char* dst = (char*)a.recvbuff + off * ts;
-      copyRange<T, false>(dst, src, len * ts, aligned);
+      if constexpr (kWire) wireGather((float*)dst, src, len, aligned);
+      else copyRange<T, false>(dst, src, len * ts, aligned);
     }
     if (tid < NCCL_AMD_MAX_RANKS) {
       bool peer = tid < n && tid != me;
@@ -3142,6 +3356,26 @@ template <typename T>
 inline ncclResult_t launchSmallFloatOp(const LaunchPlan& p) {
   if (p.wide == 1) return launchWideTyped<T, kOpWideSum>(p);
   if (p.wide == 2) return launchWideTyped<T, kOpWideAvg>(p);
+  return launchOp<T>(p);
+}
+// fp32 (its unit alone instantiates the bf16-wire kernels): a plan marked wire (NCCL_AMD_WIRE_BF16, enqueue.cc planColl)
+// runs them — a single AllReduce or ReduceScatter on the direct plan, never a group batch (launchBatch unmarks those)
+template <typename T, int OP>
+inline ncclResult_t launchWireTyped(const LaunchPlan& p) {
+  if (p.algo != ALGO_DIRECT || p.args.cbdLo || p.batch.nOps > 1 || (p.func != FUNC_ALLREDUCE && p.func != FUNC_REDUCESCATTER)) {
+    WARN("internal: no bf16-wire kernel for function %d on algorithm %d", (int)p.func, p.algo);
+    return ncclInternalError;
+  }
+  if (p.func == FUNC_ALLREDUCE)
+    NCCL_AMD_LAUNCH((collKernel<T, OP, COLL_AR>), dim3(p.nChannels), dim3(kThreads), 0, p.stream, p.args);
+  else NCCL_AMD_LAUNCH((collKernel<T, OP, COLL_RS>), dim3(p.nChannels), dim3(kThreads), 0, p.stream, p.args);
+  HIPCHECK(hipGetLastError());
+  return ncclSuccess;
+}
+template <typename T = float>  // (a template only so that the one unit that calls it, kern_f32.hip, instantiates the kernels)
+inline ncclResult_t launchF32Op(const LaunchPlan& p) {
+  if (p.wire == 1) return launchWireTyped<T, kOpWireSum>(p);
+  if (p.wire == 2) return launchWireTyped<T, kOpWireAvg>(p);
   return launchOp<T>(p);
 }
 template <typename T>
